@@ -3,7 +3,15 @@
 [+ RCCL gradient all-reduce when N > 1]) on synthetic 480x640 batches, B=8 per GPU, bf16 storage /
 fp32 accumulate (BASELINE.json configs[1]).  One process per GPU; prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--dtype bf16|fp32] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--dtype bf16|fp32] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  `--full` adds the side
+measurements after the timed steps: the dominant kernel's roofline (alone and inside one step), the step's HBM rate from the committed
+PMC profile, the exposed all-reduce time (N > 1), and on one GPU the CPU baseline, the depth-RMSE check against the oracle and the
+fp32 parity mode (the last three skipped by `--no-cpu-baseline`).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float32): model outputs, the loss and its terms, and a fixed sample of the updated parameters.  Inputs and weights
+are seeded, and the last timed step starts from the seeded weights and a fresh AdamW state (restart_from_seed), so the same
+arguments give the same inputs and the same results in every run.
 
 `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset): this process starts N child ranks of itself
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, one per GPU, RCCL) BEFORE touching the GPU,
@@ -43,7 +51,11 @@ def parse():
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements (roofline, HBM rate, all-reduce, CPU baseline, depth RMSE, fp32 mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline, depth-RMSE and fp32 legs")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="launch every kernel eagerly instead of replaying zero_grad+forward+losses+backward from one HIP graph")
     ap.add_argument("--cpu-baseline-budget-s", type=float, default=25.0)
@@ -229,6 +241,7 @@ def main():
     batch = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in b.items()}
     batch["targets"] = [{k: v.cuda() for k, v in t.items()} for t in b["targets"]]
     torch.manual_seed(100 + rank)
+    seed_state = (step.flat_p.clone(), None if step.flat_p16 is None else step.flat_p16.clone())
 
     for _ in range(a.warmup):
         step(batch)
@@ -238,10 +251,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    if a.steps == 1:
+        restart_from_seed(step, seed_state)
     barrier()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        _, total, _ = step(batch)
+    for i in range(a.steps):
+        if i == a.steps - 1 and i > 0:
+            restart_from_seed(step, seed_state)   # device-side copies, once per run: ~0.2 ms over all the timed steps
+        last_out, total, last_terms = step(batch)
     step.flush()                    # graph mode examines each loss one step late: all of them are inside the timed region
     barrier()
     el = time.perf_counter() - t0
@@ -250,9 +267,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
     ips = a.batch * world * a.steps / el
+    if a.dump_outputs and rank == 0:   # before anything else runs a step: graph mode returns the captured step's static buffers
+        dump_outputs(a.dump_outputs, last_out, total, last_terms, step)
 
     comm = None
-    if world > 1:
+    if world > 1 and a.full:
         # exposed communication: the same K steps with the bucket all-reduces switched off (every rank does this together);
         # outside the timed region, reported beside the number, not part of it
         try:
@@ -274,7 +293,7 @@ def main():
             comm = {"error": repr(exc)}
 
     roofline = None
-    if rank == 0:
+    if rank == 0 and a.full:
         roofline = dominant_kernel_roofline(lib, dtype)
         if world == 1:
             try:                    # the same kernel INSIDE the step (cold operands, neighbours on the chip): one eager step with events
@@ -297,22 +316,23 @@ def main():
                    "graph_segments": max([len(e["graph"]) for e in step._graphs.values() if e["graph"] is not None] or [0]),
                    "grad_buckets": len(step.buckets),
                    "final_loss": round(float(total), 4)},
-        "roofline": roofline,
     }
+    if roofline is not None:
+        out["roofline"] = roofline
     if comm is not None:
         out["comm"] = comm
     try:                            # step-level HBM-side traffic: PMC bytes of one step (committed profile) over the measured step time
         with open(os.path.join(ROOT, "profiles", HBM_STEP_FILE)) as f:
             hrec = json.load(f)
         hb = hrec["hbm_bytes_per_step"]
-        if a.batch == 8 and a.height == 480 and a.width == 640 and a.dtype == "bf16":
+        if a.full and a.batch == 8 and a.height == 480 and a.width == 640 and a.dtype == "bf16":
             gbps = hb / (el / a.steps) / 1e9
             out["hbm"] = {"bytes_per_step_pmc": hb, "achieved_GBps": round(gbps, 1), "frac_of_8TBps": round(gbps / PEAK_HBM_GBPS, 4),
                           "bytes_measured": "%s, commit %s - a committed PMC measurement divided by THIS run's step time" % (hrec.get("measured", "?"), hrec.get("commit", "?")),
                           "source": "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, gfx950 correction)" % HBM_STEP_FILE}
     except (OSError, KeyError, ValueError):
         pass
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         print("[bench] GPU leg done: %.2f images/s; timing the CPU baseline (oracle) ..." % ips, file=sys.stderr, flush=True)
         out["cpu_baseline"] = cpu_baseline(sd_cpu, cfg, a.cpu_baseline_budget_s)
         out["depth_rmse"] = depth_rmse_leg(sd_cpu, cfg, dtype)
@@ -330,6 +350,68 @@ def main():
         # rank that may still issue a collective, and a rank that died makes the barrier raise on the others (non-zero exit)
         dist.barrier()
         dist.destroy_process_group()
+
+
+def restart_from_seed(step, seed_state):
+    """Put the weights and the AdamW state back to where the seeded model started, so that the last timed step computes the same
+    thing in every run with the same arguments.  The steps before it train as usual, but they do not repeat bit for bit: the
+    weight-gradient kernels accumulate with float atomics (summation order varies from run to run), and the step's index ops
+    (top-k point sampling, line matching) turn last-bit weight differences into different picks within a step or two.  In place:
+    captured graphs read these buffers by address.  The dropout stream is not rewound; it is seeded and the same in every run."""
+    p, p16 = seed_state
+    step.flat_p.copy_(p)
+    if p16 is not None:
+        step.flat_p16.copy_(p16)
+    step.flat_m.zero_()
+    step.flat_v.zero_()
+    step.step_count = 0
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20
+
+
+def _sample_index(numel, device):
+    """Fixed sample of a flattened array: DUMP_SAMPLE sorted positions drawn with seed 0 (the same positions for the same size)."""
+    g = torch.Generator().manual_seed(0)
+    return torch.randint(0, numel, (DUMP_SAMPLE,), generator=g).sort().values.to(device)
+
+
+def dump_outputs(d, out, total, terms, step):
+    """What the last timed step computed, as d/<name>.npy in float32: every output tensor of the model (nested keys joined by '.'),
+    the loss and its terms (loss_terms.<name>), and params_sample - a fixed sample of the updated flat fp32 parameters, the step's
+    other result.  Arrays are written whole until the total would pass DUMP_LIMIT_BYTES; then the largest ones are replaced,
+    largest first, by the DUMP_SAMPLE values at _sample_index's positions."""
+    import re
+    import numpy as np
+    arrays = {}
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            arrays[re.sub(r"[^A-Za-z0-9_.-]", "_", name)] = v.detach()
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                if not str(k).startswith("_"):           # private entries (the matcher's prefetch handle) are no result
+                    walk("%s.%s" % (name, k) if name else str(k), x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk("%s.%d" % (name, i), x)
+
+    walk("", out)
+    arrays["loss"] = total
+    walk("loss_terms", terms)
+    arrays["params_sample"] = step.flat_p[_sample_index(step.flat_p.numel(), step.flat_p.device)]
+    size = {k: 4 * v.numel() for k, v in arrays.items()}
+    for k in sorted(arrays, key=lambda k: -size[k]):
+        if sum(size.values()) <= DUMP_LIMIT_BYTES or arrays[k].numel() <= DUMP_SAMPLE:
+            break
+        flat = arrays[k].reshape(-1)
+        arrays[k] = flat[_sample_index(flat.numel(), flat.device)]
+        size[k] = 4 * DUMP_SAMPLE
+    assert sum(size.values()) <= DUMP_LIMIT_BYTES, size
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v.float().cpu().numpy())
 
 
 def in_step_kernel_time(step, batch, gflop, peak):

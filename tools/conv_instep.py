@@ -2,7 +2,7 @@
 """Per-layer-shape time of every convolution / linear forward and data-gradient launch INSIDE the train step, from a rocprofv3 kernel
 trace of an eager bench run made with GWD_TRACE_CONV=1 (one stderr line per gwd_conv_forward call, in call order = launch order):
 
-    GWD_TRACE_CONV=1 rocprofv3 --kernel-trace --output-format csv -d D -- python3 bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline 2> conv.log
+    GWD_TRACE_CONV=1 rocprofv3 --kernel-trace --output-format csv -d D -- python3 bench.py --no-graph --steps 2 --warmup 1 --full --no-cpu-baseline 2> conv.log
     python tools/conv_instep.py D conv.log [backbone]
 
 Every gwd_conv_forward call launches exactly one kernel of the families below, so the i-th call is the i-th such kernel of the trace.

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """HBM-side traffic per kernel family from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over bench.py.
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d A -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d B -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d A -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-graph
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d B -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-graph
     python tools/hbm_by_kernel.py A B > profiles/r02_hbm_by_kernel.txt
 
 Bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024: the counters are in KiB, and on gfx950 FETCH_SIZE reports half of the bytes of
