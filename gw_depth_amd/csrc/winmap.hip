@@ -2,7 +2,8 @@
 //   gather : (B, H, W, C) token map -> (B * nWin, 49, C) windows, including zero padding to a multiple of 7 and the
 //            cyclic shift (F.pad + torch.roll + view/permute/contiguous of multiscale_transformerr.py:667-676,705-707)
 //   scatter: the inverse (window_reverse + un-shift + crop, :730-747).
-// Each is the other's backward.  16-byte channel vectors; one thread per (window token, channel vector).
+// Each is the other's backward.  16-byte channel vectors; one thread per (window token, channel vector).  A channel count whose
+// rows are not whole 16-byte vectors (C % 4 in fp32, C % 8 in bf16) takes the same single-map kernel one ELEMENT per thread.
 #include "common.h"
 
 namespace {
@@ -17,9 +18,14 @@ template <typename T> __device__ __forceinline__ uint4 add_vec(const uint4 &a, c
     for (int e = 0; e < N; ++e) pr[e] = from_f32<T>(to_f32(pa[e]) + to_f32(pb[e]));
     return r;
 }
+template <typename T> __device__ __forceinline__ T add_vec(const T &a, const T &b) { return from_f32<T>(to_f32(a) + to_f32(b)); }
 
-template <bool GATHER, typename T>
-__global__ void winmap_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, const uint4 *__restrict__ res, int B, int H, int W,
+template <typename V> __device__ __forceinline__ V zero_vec() { return from_f32<V>(0.f); }
+template <> __device__ __forceinline__ uint4 zero_vec<uint4>() { return make_uint4(0u, 0u, 0u, 0u); }
+
+// V: what one thread moves - uint4 (CV = 16-byte vectors per token) or one element of T (CV = C)
+template <bool GATHER, typename T, typename V>
+__global__ void winmap_kernel(const V *__restrict__ src, V *__restrict__ dst, const V *__restrict__ res, int B, int H, int W,
                               int CV, int shift) {
     const int Hp = (H + 6) / 7 * 7, Wp = (W + 6) / 7 * 7, nwx = Wp / 7, nwy = Hp / 7;
     const int64_t total = (int64_t)B * Hp * Wp * CV;
@@ -38,7 +44,7 @@ __global__ void winmap_kernel(const uint4 *__restrict__ src, uint4 *__restrict__
         const bool inside = py < H && px < W;
         const int64_t map_idx = (((int64_t)b * H + py) * W + px) * CV + cv;
         if (GATHER) {
-            dst[i] = inside ? src[map_idx] : make_uint4(0u, 0u, 0u, 0u);
+            dst[i] = inside ? src[map_idx] : zero_vec<V>();
         } else if (inside) {
             dst[map_idx] = res ? add_vec<T>(src[i], res[map_idx]) : src[i];     // window reverse (+ the block's residual stream)
         }
@@ -120,19 +126,33 @@ extern "C" int gwd_window_map(const void *src, void *dst, const void *residual, 
     if (gather && residual) return -1;
     const int esz = dtype == GWD_BF16 ? 2 : (dtype == GWD_F32 ? 4 : 0);
     if (!esz) return -2;
-    if ((C * esz) % 16) return -4;
-    const int CV = C * esz / 16;
+    const bool vec = (C * esz) % 16 == 0;
+    const int CV = vec ? C * esz / 16 : C;
     const int Hp = (H + 6) / 7 * 7, Wp = (W + 6) / 7 * 7;
     const int64_t total = (int64_t)B * Hp * Wp * CV;
     int64_t nb = (total + 255) / 256;
     const int grid = (int)(nb > 8192 ? 8192 : nb);
+    hipStream_t st = (hipStream_t)stream;
+    if (!vec) {                                   // rows that are not whole 16-byte vectors: one element per thread
+        if (dtype == GWD_BF16) {
+            const __bf16 *s = (const __bf16 *)src, *r = (const __bf16 *)residual;
+            if (gather) winmap_kernel<true, __bf16, __bf16><<<grid, 256, 0, st>>>(s, (__bf16 *)dst, nullptr, B, H, W, CV, shift);
+            else winmap_kernel<false, __bf16, __bf16><<<grid, 256, 0, st>>>(s, (__bf16 *)dst, r, B, H, W, CV, shift);
+        } else {
+            const float *s = (const float *)src, *r = (const float *)residual;
+            if (gather) winmap_kernel<true, float, float><<<grid, 256, 0, st>>>(s, (float *)dst, nullptr, B, H, W, CV, shift);
+            else winmap_kernel<false, float, float><<<grid, 256, 0, st>>>(s, (float *)dst, r, B, H, W, CV, shift);
+        }
+        GWD_CHECK_LAUNCH();
+        return 0;
+    }
     const uint4 *r4 = (const uint4 *)residual;
     if (gather)
-        winmap_kernel<true, float><<<grid, 256, 0, (hipStream_t)stream>>>((const uint4 *)src, (uint4 *)dst, nullptr, B, H, W, CV, shift);
+        winmap_kernel<true, float, uint4><<<grid, 256, 0, st>>>((const uint4 *)src, (uint4 *)dst, nullptr, B, H, W, CV, shift);
     else if (dtype == GWD_BF16)
-        winmap_kernel<false, __bf16><<<grid, 256, 0, (hipStream_t)stream>>>((const uint4 *)src, (uint4 *)dst, r4, B, H, W, CV, shift);
+        winmap_kernel<false, __bf16, uint4><<<grid, 256, 0, st>>>((const uint4 *)src, (uint4 *)dst, r4, B, H, W, CV, shift);
     else
-        winmap_kernel<false, float><<<grid, 256, 0, (hipStream_t)stream>>>((const uint4 *)src, (uint4 *)dst, r4, B, H, W, CV, shift);
+        winmap_kernel<false, float, uint4><<<grid, 256, 0, st>>>((const uint4 *)src, (uint4 *)dst, r4, B, H, W, CV, shift);
     GWD_CHECK_LAUNCH();
     return 0;
 }

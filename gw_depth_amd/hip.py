@@ -656,18 +656,28 @@ class HipLibrary:
         self._check(self.lib.gwd_upsample_taps_fold(_ptr(D), _ptr(dw), Cout, Cin, self._stream(D, dw)), "gwd_upsample_taps_fold")
 
     def tokattn_pair_forward(self, q, q2, k, v, o, o2, scale):
-        """Both class tokens against the same k / v in one launch (bf16): q, q2 -> o, o2."""
+        """Both class tokens against the same k / v in one launch (bf16): q, q2 -> o, o2.  False when the library declines the
+        call (-4: an operand that is not 8-byte aligned, a stride that is not a multiple of 4, an e it has no kernel for) - it does so
+        before launching anything, and the caller issues two tokattn_forward calls."""
         W, N, H, _ = q.shape
         s = [_strided(t) for t in (q, q2, k, v, o, o2)]
-        self._check(self.lib.gwd_tokattn_pair_forward(*[ctypes.byref(x) for x in s], W, H, k.shape[3], scale, dtype_code(q),
-                                                      self._stream(q, q2, k, v, o, o2)), "gwd_tokattn_pair_forward")
+        rc = self.lib.gwd_tokattn_pair_forward(*[ctypes.byref(x) for x in s], W, H, k.shape[3], scale, dtype_code(q),
+                                               self._stream(q, q2, k, v, o, o2))
+        if rc == -4:
+            return False
+        self._check(rc, "gwd_tokattn_pair_forward")
+        return True
 
     def tokattn_pair_backward(self, q, q2, k, v, go, go2, gq, gq2, gk, gv, scale):
-        """gq, gq2 per token; gk, gv summed over both tokens."""
+        """gq, gq2 per token; gk, gv summed over both tokens.  False when the library declines the call (see tokattn_pair_forward)."""
         W, N, H, _ = q.shape
         s = [_strided(t) for t in (q, q2, k, v, go, go2, gq, gq2, gk, gv)]
-        self._check(self.lib.gwd_tokattn_pair_backward(*[ctypes.byref(x) for x in s], W, H, k.shape[3], scale, dtype_code(q),
-                                                       self._stream(q, go, gq)), "gwd_tokattn_pair_backward")
+        rc = self.lib.gwd_tokattn_pair_backward(*[ctypes.byref(x) for x in s], W, H, k.shape[3], scale, dtype_code(q),
+                                                self._stream(q, go, gq))
+        if rc == -4:
+            return False
+        self._check(rc, "gwd_tokattn_pair_backward")
+        return True
 
     def certain_sample(self, small, large, coords, edges, sample_num):
         """small (B,1,hs,ws), large (B,1,H,W) fp32; edges (I+1,) fp32; coords (B,S,1,2) fp32 out."""
@@ -808,14 +818,20 @@ class HipLibrary:
                                             self._stream(src, dst)), "gwd_window_map")
 
     def window_map_multi(self, srcs, dsts, B, H, W, Cs, shift, gather, residuals=None):
-        """gwd_window_map for up to 4 maps of one geometry in one launch (residuals: list with None entries, or None)."""
+        """gwd_window_map for up to 4 maps of one geometry in one launch (residuals: list with None entries, or None).  False when the
+        library declines the call (-4: a channel count whose rows are not whole 16-byte vectors) - before launching anything; the caller
+        issues window_map per map."""
         n = len(srcs)
         vpn, i32n = ctypes.c_void_p * n, ctypes.c_int32 * n
         res = [None] * n if residuals is None else list(residuals)
         addr = lambda t: None if t is None else _ptr(t).value
-        self._check(self.lib.gwd_window_map_multi(vpn(*[addr(t) for t in srcs]), vpn(*[addr(t) for t in dsts]), vpn(*[addr(t) for t in res]),
-                                                  i32n(*[int(c) for c in Cs]), n, B, H, W, shift, int(gather), dtype_code(srcs[0]),
-                                                  self._stream(*srcs, *dsts)), "gwd_window_map_multi")
+        rc = self.lib.gwd_window_map_multi(vpn(*[addr(t) for t in srcs]), vpn(*[addr(t) for t in dsts]), vpn(*[addr(t) for t in res]),
+                                           i32n(*[int(c) for c in Cs]), n, B, H, W, shift, int(gather), dtype_code(srcs[0]),
+                                           self._stream(*srcs, *dsts))
+        if rc == -4:
+            return False
+        self._check(rc, "gwd_window_map_multi")
+        return True
 
     def sqnorm(self, g, sq, n):
         self._check(self.lib.gwd_sqnorm(_ptr(g), _ptr(sq), n, self._stream(g, sq)), "gwd_sqnorm")

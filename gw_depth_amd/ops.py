@@ -1551,7 +1551,9 @@ class _TokAttnPairFn(torch.autograd.Function):
         W, N, H, R = q.shape
         o = torch.empty((W, N, H, R), dtype=q.dtype, device=q.device)
         o2 = torch.empty_like(o)
-        _lib().tokattn_pair_forward(q, q2, k, v, o, o2, scale)
+        if _lib().tokattn_pair_forward(q, q2, k, v, o, o2, scale) is False:     # declined (alignment): the two single calls
+            _lib().tokattn_forward(q, k, v, o, scale)
+            _lib().tokattn_forward(q2, k, v, o2, scale)
         ctx.save_for_backward(q, q2, k, v)
         ctx.scale = scale
         return o.view(W, N, H * R), o2.view(W, N, H * R)
@@ -1564,7 +1566,11 @@ class _TokAttnPairFn(torch.autograd.Function):
         gq, gq2 = torch.empty_like(go), torch.empty_like(go)
         gk = torch.empty(k.shape, dtype=k.dtype, device=k.device)
         gv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
-        _lib().tokattn_pair_backward(q, q2, k, v, go, go2, gq, gq2, gk, gv, ctx.scale)
+        if _lib().tokattn_pair_backward(q, q2, k, v, go, go2, gq, gq2, gk, gv, ctx.scale) is False:
+            gk2, gv2 = torch.empty_like(gk), torch.empty_like(gv)            # declined: two single calls, summed as autograd sums two nodes
+            _lib().tokattn_backward(q, k, v, go, gq, gk, gv, ctx.scale)
+            _lib().tokattn_backward(q2, k, v, go2, gq2, gk2, gv2, ctx.scale)
+            gk, gv = gk + gk2, gv + gv2
         return gq, gq2, gk, gv, None
 
 
@@ -1614,6 +1620,14 @@ class _WindowScatterFn(torch.autograd.Function):
         return gw, None, None, None, None, (g.view(rshape) if rshape else None)
 
 
+def _window_map_each(srcs, dsts, B, H, W, Cs, shift, gather, residuals=None):
+    """window_map_multi, or - when the library declines the joint launch - window_map per map."""
+    if _lib().window_map_multi(srcs, dsts, B, H, W, Cs, shift, gather, residuals=residuals) is not False:
+        return
+    for i, (s, d, c) in enumerate(zip(srcs, dsts, Cs)):
+        _lib().window_map(s, d, B, H, W, c, shift, gather, residual=None if residuals is None else residuals[i])
+
+
 class _WindowGatherMultiFn(torch.autograd.Function):
     """window_gather of several maps of one geometry (features + class tokens of a Swin block) as ONE launch each way."""
 
@@ -1623,7 +1637,7 @@ class _WindowGatherMultiFn(torch.autograd.Function):
         B, H, W = xs[0].shape[:3]
         Hp, Wp = (H + 6) // 7 * 7, (W + 6) // 7 * 7
         outs = [torch.empty((B * (Hp // 7) * (Wp // 7), 49, x.shape[-1]), dtype=x.dtype, device=x.device) for x in xs]
-        _lib().window_map_multi(xs, outs, B, H, W, [x.shape[-1] for x in xs], shift, True)
+        _window_map_each(xs, outs, B, H, W, [x.shape[-1] for x in xs], shift, True)
         ctx.cfg = (B, H, W, shift, [x.shape[-1] for x in xs])
         return tuple(outs)
 
@@ -1632,7 +1646,7 @@ class _WindowGatherMultiFn(torch.autograd.Function):
         B, H, W, shift, Cs = ctx.cfg
         gs = [g.contiguous() for g in gs]
         gxs = [torch.empty((B, H, W, c), dtype=g.dtype, device=g.device) for g, c in zip(gs, Cs)]
-        _lib().window_map_multi(gs, gxs, B, H, W, Cs, shift, False)
+        _window_map_each(gs, gxs, B, H, W, Cs, shift, False)
         return (None,) + tuple(gxs)
 
 
@@ -1645,7 +1659,7 @@ class _WindowScatterMultiFn(torch.autograd.Function):
         ress = [None if r is None else r.contiguous() for r in ts[n:]]
         Cs = [w.shape[-1] for w in wins]
         outs = [torch.empty((B, H, W, c), dtype=w.dtype, device=w.device) for w, c in zip(wins, Cs)]
-        _lib().window_map_multi(wins, outs, B, H, W, Cs, shift, False, residuals=ress)
+        _window_map_each(wins, outs, B, H, W, Cs, shift, False, residuals=ress)
         ctx.cfg = (B, H, W, shift, Cs, [tuple(w.shape) for w in wins], [r is not None and tuple(r.shape) for r in ts[n:]])
         return tuple(outs)
 
@@ -1654,7 +1668,7 @@ class _WindowScatterMultiFn(torch.autograd.Function):
         B, H, W, shift, Cs, shapes, rshapes = ctx.cfg
         gs = [g.contiguous() for g in gs]
         gws = [torch.empty(sh, dtype=g.dtype, device=g.device) for g, sh in zip(gs, shapes)]
-        _lib().window_map_multi(gs, gws, B, H, W, Cs, shift, True)
+        _window_map_each(gs, gws, B, H, W, Cs, shift, True)
         return (None,) * 5 + tuple(gws) + tuple((g.view(rs) if rs else None) for g, rs in zip(gs, rshapes))
 
 

@@ -407,13 +407,16 @@ int gwd_inorm_gelu_backward(const void *gy, const void *u, const float *stat, fl
 
 /* Window partition (gather != 0) / reverse (gather == 0) of a (B,H,W,C) token map into (B*nWin,49,C) 7x7 windows
  * with zero padding to multiples of 7 and cyclic shift `shift` (src/models/multiscale_transformerr.py:667-676,
- * 705-707 / 730-747).  C * sizeof(dtype) must be a multiple of 16.  residual (reverse only, may be NULL): a (B,H,W,C)
+ * 705-707 / 730-747).  Rows of whole 16-byte vectors (C * sizeof(dtype) % 16 == 0) move 16 bytes per thread, any other C one
+ * element per thread.  residual (reverse only, may be NULL): a (B,H,W,C)
  * map added to the result - the block's residual stream, `x = shortcut + x` of :749.                           */
 int gwd_window_map(const void *src, void *dst, const void *residual, int32_t B, int32_t H, int32_t W, int32_t C, int32_t shift,
                    int32_t gather, int32_t dtype, void *stream);
 /* The same for n <= GWD_WINMAP_JOBS maps of one geometry (B, H, W, shift) and channel counts C[i] in ONE launch: the three maps a
  * Swin block with class tokens hands over together (features, depth tokens, seg tokens: multiscale_transformerr.py:700-747).
- * src / dst / residual: HOST arrays of n device pointers (residual, or single entries of it, may be NULL).        */
+ * src / dst / residual: HOST arrays of n device pointers (residual, or single entries of it, may be NULL).  16-byte rows only:
+ * -4, before anything is launched, when some C[i] * sizeof(dtype) is not a multiple of 16 (the caller issues gwd_window_map
+ * per map).                                                                                                        */
 #define GWD_WINMAP_JOBS 4
 int gwd_window_map_multi(const void *const *src, void *const *dst, const void *const *residual, const int32_t *C, int32_t n,
                          int32_t B, int32_t H, int32_t W, int32_t shift, int32_t gather, int32_t dtype, void *stream);
