@@ -6,6 +6,13 @@ Public surface = the reference's own model API (/root/reference/src/models/__ini
 from .config import Config
 
 
+def __getattr__(name):
+    if name == "InferenceSession":          # lazily: importing the package must not pull torch in
+        from .infer import InferenceSession
+        return InferenceSession
+    raise AttributeError(name)
+
+
 def build_model(args):
     """Drop-in for the reference's models.build_model (glassrgbd.py:509-579)."""
     import torch

@@ -337,13 +337,33 @@ class SegLoss(nn.Module):
 
 
 class PostProcessLine(nn.Module):
-    """PostProcess_Line 'prediction' branch, glassrgbd.py:452-479."""
+    """PostProcess_Line, glassrgbd.py:452-506: the three branches 'prediction' (reads outputs["pred_lines"]), 'prediction_POST'
+    (reads outputs["POST_pred_lines"]) and 'ground_truth' (outputs is a list of target dicts; result keys labels, lines,
+    image_id); any other output_type is an AssertionError.
+
+    Two departures from the reference, both where it fails: every branch takes the FIRST FOUR coordinates of a line (the
+    reference multiplies by a 4-wide scale and raises on the model's 6-wide lines), and 'ground_truth' scales the lines of
+    image i by row i of target_sizes (the reference broadcasts (n,4) * (B,4), which only works for B == 1, where the two agree)."""
+
+    @staticmethod
+    def _scale(target_sizes):
+        img_h, img_w = target_sizes.unbind(1)
+        return torch.stack([img_w, img_h, img_w, img_h], dim=1)
 
     @torch.no_grad()
     def forward(self, outputs, target_sizes, output_type="prediction"):
-        prob = F.softmax(outputs["pred_logits"].float(), -1)
-        scores, labels = prob[..., :-1].max(-1)
-        img_h, img_w = target_sizes.unbind(1)
-        scale = torch.stack([img_w, img_h, img_w, img_h], dim=1)
-        lines = outputs["pred_lines"][..., :4] * scale[:, None, :]
-        return [{"scores": s, "labels": l, "lines": b} for s, l, b in zip(scores, labels, lines)]
+        if output_type in ("prediction", "prediction_POST"):
+            out_line = outputs["pred_lines" if output_type == "prediction" else "POST_pred_lines"]
+            assert len(outputs["pred_logits"]) == len(target_sizes)
+            assert target_sizes.shape[1] == 2
+            prob = F.softmax(outputs["pred_logits"].float(), -1)
+            scores, labels = prob[..., :-1].max(-1)
+            lines = out_line[..., :4] * self._scale(target_sizes)[:, None, :]
+            return [{"scores": s, "labels": l, "lines": b} for s, l, b in zip(scores, labels, lines)]
+        if output_type == "ground_truth":
+            assert len(outputs) == len(target_sizes)
+            assert target_sizes.shape[1] == 2
+            scale = self._scale(target_sizes)
+            return [{"labels": dic["labels"], "lines": dic["lines"][..., :4] * scale[i], "image_id": dic["image_id"]}
+                    for i, dic in enumerate(outputs)]
+        assert False, "unknown output_type %r" % (output_type,)

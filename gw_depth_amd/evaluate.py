@@ -91,7 +91,8 @@ class DenseMetrics:
 @torch.no_grad()
 def evaluate(model, criterions, postprocessors, data_loader, base_ds, device, output_dir, args, save_dir=None, epoch=0,
              save_dense=False, save_line=False):
-    """Same signature and stats as the reference's evaluate() (engine_glassrgbd.py:174-345)."""
+    """Same signature and stats as the reference's evaluate() (engine_glassrgbd.py:174-345).  `model` is the module or an
+    infer.InferenceSession over it (frozen weight copies, graph replay): each batch's outputs are consumed before the next call."""
     if save_dense or save_line:
         raise NotImplementedError("save_dense / save_line write visualisations; outside the accelerated path (SURVEY.md §2)")
     model.eval()

@@ -33,6 +33,7 @@ ENTRY_POINTS = [
     "gwd_anchor_depth_forward", "gwd_anchor_depth_backward", "gwd_mha_flash_forward", "gwd_mha_flash_backward",
     "gwd_ref_scores_forward", "gwd_ref_scores_backward", "gwd_ref_mix_forward", "gwd_ref_mix_backward", "gwd_unpad_add_batch", "gwd_stem_pack", "gwd_stem_forward", "gwd_pos_sine", "gwd_silog_finalize", "gwd_psp_pool_forward", "gwd_psp_pool_backward",
     "gwd_match_cost", "gwd_set_losses_forward", "gwd_set_losses_backward", "gwd_resample_u8_pass", "gwd_gather2d", "gwd_point_sample_backward_gather", "gwd_point_sample_framed_forward", "gwd_point_sample_framed_backward", "gwd_stride_place", "gwd_color_adjust", "gwd_bmm",
+    "gwd_dense_postprocess", "gwd_line_postprocess",
 ]
 
 
@@ -220,6 +221,8 @@ class HipLibrary:
         L.gwd_query_workspace.argtypes = [i32, ctypes.POINTER(ctypes.c_int64), i32]
         L.gwd_query_workspace.restype = ctypes.c_int64
         L.gwd_eval_accumulate.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, i64, f32, f32, i32, i32, vp]
+        L.gwd_dense_postprocess.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp]
+        L.gwd_line_postprocess.argtypes = [vp] * 7 + [i32, i32, i32, f32, vp]
         L.gwd_softmax_masked_forward.argtypes = [vp, vp, vp, i64, i32, i64, ctypes.c_float, i32, vp]
         L.gwd_softmax_scaled_backward.argtypes = [vp, vp, vp, i64, i32, ctypes.c_float, i32, vp]
         L.gwd_resample_backward_sep.argtypes = [vp, vp, vp] + [i32] * 9 + [vp]
@@ -437,6 +440,35 @@ class HipLibrary:
             _ptr(workspace), _ptr(measures), _ptr(running), _ptr(confusion), B, HW, float(dmin), float(dmax),
             dtype_code(pred) if pred is not None else F32, dtype_code(seg) if seg is not None else F32,
             self._stream(pred, gt, seg, seg_gt, workspace, measures, running, confusion)), "gwd_eval_accumulate")
+
+    def dense_postprocess(self, depth, seg, seg_strides, sizes, depth_out, depth_mm, label, B, H, W, dmin, dmax):
+        """gwd_dense_postprocess.  seg may be a strided view: seg_strides = (image, pixel, class) element strides; sizes (B,2)
+        int32 or None; depth_mm uint16 or None."""
+        for t, dt in ((sizes, torch.int32), (depth_out, torch.float32), (depth_mm, torch.uint16), (label, torch.uint8)):
+            if t is not None and t.dtype != dt:
+                raise TypeError("gwd_dense_postprocess: expected %s, got %s" % (dt, t.dtype))
+        n = B * H * W
+        if depth.numel() != n or depth_out.numel() != n or label.numel() != n or (depth_mm is not None and depth_mm.numel() != n) \
+                or (sizes is not None and sizes.numel() != 2 * B):
+            raise ValueError("gwd_dense_postprocess: operand sizes do not match (B, H, W) = (%d, %d, %d)" % (B, H, W))
+        sb, sp, sc = (int(v) for v in seg_strides)
+        self._check(self.lib.gwd_dense_postprocess(
+            _ptr(depth), ctypes.c_void_p(seg.data_ptr()), sb, sp, sc, _ptr(sizes), _ptr(depth_out), _ptr(depth_mm), _ptr(label),
+            B, H, W, float(dmin), float(dmax), dtype_code(depth), dtype_code(seg),
+            self._stream(depth, seg, sizes, depth_out, depth_mm, label)), "gwd_dense_postprocess")
+
+    def line_postprocess(self, logits, lines, sizes, scores, lines_px, order, count, B, Q, ld, thresh):
+        """gwd_line_postprocess: logits (B,Q,2) / lines (B,Q,ld) fp32, sizes (B,2) int32; Q <= 1024."""
+        for t, dt in ((logits, torch.float32), (lines, torch.float32), (sizes, torch.int32), (scores, torch.float32),
+                      (lines_px, torch.float32), (order, torch.int32), (count, torch.int32)):
+            if t.dtype != dt:
+                raise TypeError("gwd_line_postprocess: expected %s, got %s" % (dt, t.dtype))
+        if logits.numel() != B * Q * 2 or lines.numel() != B * Q * ld or sizes.numel() != 2 * B or scores.numel() != B * Q \
+                or lines_px.numel() != B * Q * 4 or order.numel() != B * Q or count.numel() != B:
+            raise ValueError("gwd_line_postprocess: operand sizes do not match (B, Q, ld) = (%d, %d, %d)" % (B, Q, ld))
+        self._check(self.lib.gwd_line_postprocess(
+            _ptr(logits), _ptr(lines), _ptr(sizes), _ptr(scores), _ptr(lines_px), _ptr(order), _ptr(count), B, Q, ld, float(thresh),
+            self._stream(logits, lines, sizes, scores, lines_px, order, count)), "gwd_line_postprocess")
 
     def plane_loss_forward(self, depth, valid, tri, n_planes, P, H, W, min_area, workspace, stats, loss):
         self._check(self.lib.gwd_plane_loss_forward(_ptr(depth), _ptr(valid), _ptr(tri), _ptr(n_planes), P, H, W, min_area,

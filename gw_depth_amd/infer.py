@@ -1,0 +1,274 @@
+"""Inference session: what engine.TrainStep is for training, for the forward alone.
+
+The plain path (`model.eval(); model(samples)` under no_grad) makes every bf16 / BN-folded weight copy again on every call,
+launches every kernel from Python and ends at raw tensors.  An InferenceSession
+
+* freezes the weight copies: it owns an ops.WeightCache(frozen=True) over the storage of every parameter and buffer, so a
+  copy is made when its weight is first seen (the first call) and stays; refresh() rewrites all of them in place with one launch;
+* replays a captured HIP graph per input signature (B, H, W): forward and post-processing, on one private stream, out of one
+  memory pool, least recently used signature dropped beyond engine.MAX_GRAPHS;
+* finishes on the device: the un-padded sizes from the pad mask, the dense post-processing (gwd_dense_postprocess) and
+  the line post-processing with a ranking (gwd_line_postprocess), both inside the captured graph, no host sync anywhere.
+"""
+import contextlib
+import gc
+import warnings
+from collections import OrderedDict
+
+import torch
+
+from . import engine, ops
+from .model import NestedTensor, nested_tensor_from_tensor_list
+
+RESULT_KEYS = ("depth", "depth_mm", "labels", "scores", "lines", "order", "count", "sizes")
+
+
+def _count_memsets_in(fn):
+    """Run fn() under the profiler and count the hipMemsetAsync runtime calls it makes (the audit of TrainStep._count_memsets:
+    memset nodes do not replay correctly in HIP graphs on this ROCm).  -1: no tracer on this host, fn() has still run once."""
+    from torch.profiler import ProfilerActivity, profile
+    try:
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(1 for e in prof.events() if e.name == "hipMemsetAsync")
+    except Exception as exc:
+        warnings.warn("gw_depth_amd: capture audit unavailable (%s)" % exc)
+        fn()
+        return -1
+
+
+class InferenceSession:
+    """sess = InferenceSession(model, compute_dtype=torch.bfloat16, graph=True, min_depth=..., max_depth=..., score_thresh=0.6)
+
+    sess(samples, reflc_mat=None, img_name=None, taps=None) -> the model's own output dict (the call signature is the
+    model's, so a session can stand where the reference passes `model`; .eval() returns the session, .train() raises).
+    sess.predict(samples, target_sizes=None, copy=False) -> dict(depth (B,H,W) fp32 clamped to [min_depth, max_depth],
+    depth_mm uint16, labels uint8, scores (B,Q), lines (B,Q,4) pixels, order (B,Q) int32, count (B,) int32, sizes (B,2) int32).
+    `samples`: NestedTensor, (B,3,H,W) tensor or list of (3,h,w) tensors.  A call leaves the model in eval mode.
+
+    LIFETIME OF OUTPUTS.  With graph=True the results of a replayed signature are the graph's static tensors: they are valid
+    until the next call with the same signature (B, H, W), which overwrites them in place (or until more than engine.MAX_GRAPHS
+    other signatures have pushed it out of the cache).  Clone what must live longer, or use
+    predict(..., copy=True), which returns fresh tensors.  Eager calls (graph=False, a call with taps, a refused capture)
+    return fresh tensors anyway.
+
+    FROZEN WEIGHTS.  compute_dtype=torch.bfloat16: the kernel-side copies are made once.  After load_state_dict or optimizer
+    steps call refresh(): one gwd_weight_prep_batch launch rewrites the copies in place, so captured graphs (which read them
+    by address) stay valid.  The cache is keyed by address: parameter storage must not move after the session is built -
+    TrainStep.__init__ moves every parameter into its flat buffer, so build the session AFTER the TrainStep; refresh() checks
+    and raises.  compute_dtype=torch.float32 has no copies to freeze (the kernels read the parameters themselves).
+
+    A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
+    from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
+
+    def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6):
+        if compute_dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
+        self.model = model
+        self.compute_dtype = compute_dtype
+        self.use_graph = bool(graph)
+        self.min_depth, self.max_depth, self.score_thresh = float(min_depth), float(max_depth), float(score_thresh)
+        self._graphs = OrderedDict()
+        self._pool = None
+        self._gstream = None
+        self._addr = self._addresses()
+        spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in self._storage() if t.numel()]
+        self.weights = ops.WeightCache(spans, frozen=True) if compute_dtype == torch.bfloat16 else None
+
+    # ------------------------------------------------------------------ the reference passes `model`
+    def eval(self):
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            raise RuntimeError("an InferenceSession does not train; use engine.TrainStep on the model")
+        return self
+
+    def to(self, *a, **k):
+        raise RuntimeError("an InferenceSession is bound to the addresses of its model's parameters; move the model first, "
+                           "then build the session")
+
+    # ------------------------------------------------------------------ weights
+    def _storage(self):
+        return [p.data for p in self.model.parameters()] + [b for b in self.model.buffers() if b.is_floating_point()]
+
+    def _addresses(self):
+        return [t.data_ptr() for t in self._storage()]
+
+    def refresh(self):
+        """The weights changed in place (load_state_dict, optimizer steps): bring the frozen copies up to date - the folded
+        FrozenBN scale / shift pairs and, in ONE launch, every bf16 weight copy - on the session's stream, in place."""
+        if self._addresses() != self._addr:
+            raise RuntimeError("gw_depth_amd: parameter storage moved after the InferenceSession was built (a TrainStep built "
+                               "later moves every parameter into its flat buffer; model.to() re-allocates): build a new session")
+        with torch.no_grad(), self._on_stream():
+            for m in self.model.modules():
+                if hasattr(m, "folded"):
+                    m.folded()
+            if self.weights is not None:
+                self.weights.refresh()
+        return self
+
+    # ------------------------------------------------------------------ one sync-free pass
+    def _forward(self, images, mask, taps=None):
+        model = self.model
+        if model.training:
+            model.eval()
+        keep = model.compute_dtype
+        model.compute_dtype = self.compute_dtype
+        weights = self.weights if images.is_cuda else None
+        if weights is not None:
+            weights.begin_pass()
+        try:
+            with torch.no_grad():
+                return model(NestedTensor(images, mask), taps=taps)
+        finally:
+            if weights is not None:
+                weights.end_pass()
+            model.compute_dtype = keep
+
+    def _post(self, out, mask, target):
+        """Device post-processing of one forward.  target (B,2) int32: the size the lines are scaled to, rows < 0 = the
+        un-padded input size."""
+        with torch.no_grad():
+            sizes = torch.stack([(~mask[:, :, 0]).sum(1, dtype=torch.int32), (~mask[:, 0, :]).sum(1, dtype=torch.int32)], dim=1)
+            depth, mm, labels = ops.dense_postprocess(out["pred_depth"][-1], out["pred_seg"], sizes, self.min_depth, self.max_depth)
+            lsz = torch.where(target >= 0, target, sizes)
+            scores, lines, order, count = ops.line_postprocess(out["pred_logits"], out["pred_lines"], lsz, self.score_thresh)
+        return {"depth": depth, "depth_mm": mm, "labels": labels, "scores": scores, "lines": lines, "order": order,
+                "count": count, "sizes": sizes}
+
+    def _pass(self, st):
+        out = self._forward(st["images"], st["mask"])
+        return out, self._post(out, st["mask"], st["target"])
+
+    # ------------------------------------------------------------------ graphs
+    def _graph_stream(self):
+        if self._gstream is None:
+            self._gstream = torch.cuda.Stream()
+        return self._gstream
+
+    @contextlib.contextmanager
+    def _on_stream(self):
+        """Everything a graph-mode session launches runs on its one private stream, ordered behind the caller's stream on the
+        way in and in front of it on the way out (no host sync).  An eager session stays on the caller's stream."""
+        if not (self.use_graph and torch.cuda.is_available()):
+            yield
+            return
+        side = self._graph_stream()
+        side.wait_stream(torch.cuda.current_stream())
+        try:
+            with torch.cuda.stream(side):
+                yield
+        finally:
+            torch.cuda.current_stream().wait_stream(side)
+
+    def _count_memsets(self, st):
+        return _count_memsets_in(lambda: self._pass(st))
+
+    def _graph_entry(self, images, mask):
+        key = tuple(int(images.shape[i]) for i in (0, 2, 3))
+        ent = self._graphs.get(key)
+        if ent is not None:
+            self._graphs.move_to_end(key)
+            return ent
+        while len(self._graphs) >= engine.MAX_GRAPHS:      # bounded cache; the executables go, the shared pool keeps the memory
+            self._graphs.popitem(last=False)
+        st = {"images": images.clone(), "mask": mask.clone(),
+              "target": torch.full((key[0], 2), -1, dtype=torch.int32, device=images.device)}
+        with self._on_stream():
+            self._pass(st)                                 # allocator, lazily built caches, the frozen weight copies
+            memsets = self._count_memsets(st)              # second warm-up pass, audited
+        reason = None
+        if memsets < 0:
+            reason = "the capture audit (torch.profiler runtime-call trace) is not available on this host"
+        elif memsets:
+            reason = ("%d hipMemsetAsync call(s) in the forward (ATen multi-block reductions zero their semaphores that way); "
+                      "memset nodes do not replay correctly in HIP graphs on this ROCm" % memsets)
+        if reason is not None:
+            warnings.warn("gw_depth_amd: HIP-graph capture refused for input signature %r, running eager: %s" % (key, reason))
+            ent = self._graphs[key] = {"graph": None, "reason": reason}
+            return ent
+        if self._pool is None:
+            self._pool = torch.cuda.graph_pool_handle()
+        torch.cuda.synchronize()
+        gc.collect()
+        g = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.stream(self._graph_stream()):
+                g.capture_begin(pool=self._pool, capture_error_mode="thread_local")
+                try:
+                    res = self._pass(st)
+                finally:
+                    g.capture_end()
+        except RuntimeError as e:                          # capture invalidated: keep serving, eagerly, and say so
+            torch.cuda.synchronize()
+            warnings.warn("gw_depth_amd: HIP-graph capture failed for input signature %r, running eager: %s" % (key, e))
+            ent = self._graphs[key] = {"graph": None, "reason": str(e)}
+            return ent
+        ent = self._graphs[key] = {"graph": g, "static": st, "result": res}
+        return ent
+
+    @property
+    def graphs(self):
+        """{(B, H, W): {"captured": bool, "reason": why not}} for every signature in the cache, oldest first."""
+        return OrderedDict((k, {"captured": e["graph"] is not None, "reason": e.get("reason")}) for k, e in self._graphs.items())
+
+    # ------------------------------------------------------------------ calls
+    @staticmethod
+    def _decompose(samples):
+        if isinstance(samples, (list, tuple, torch.Tensor)):
+            samples = nested_tensor_from_tensor_list(samples)
+        images, mask = samples.decompose()
+        if mask is None:
+            mask = torch.zeros((images.shape[0],) + tuple(images.shape[-2:]), dtype=torch.bool, device=images.device)
+        return images, mask
+
+    def _target(self, target_sizes, B, device):
+        if target_sizes is None:
+            return None
+        t = torch.as_tensor(target_sizes).to(device=device, dtype=torch.int32, non_blocking=True)
+        if tuple(t.shape) != (B, 2):
+            raise ValueError("target_sizes must be (B, 2) = (h, w) per image, got %s" % (tuple(t.shape),))
+        return t
+
+    def _run(self, samples, target_sizes, want_post, taps=None):
+        images, mask = self._decompose(samples)
+        B = images.shape[0]
+        target = self._target(target_sizes, B, images.device)
+        if self.use_graph and images.is_cuda and taps is None:
+            ent = self._graph_entry(images, mask)
+            if ent["graph"] is not None:
+                st = ent["static"]
+                with self._on_stream():
+                    st["images"].copy_(images, non_blocking=True)
+                    st["mask"].copy_(mask, non_blocking=True)
+                    if target is None:
+                        st["target"].fill_(-1)
+                    else:
+                        st["target"].copy_(target, non_blocking=True)
+                    ent["graph"].replay()
+                return ent["result"]
+        with self._on_stream():
+            out = self._forward(images, mask, taps=taps)
+            post = None
+            if want_post:
+                if target is None:
+                    target = torch.full((B, 2), -1, dtype=torch.int32, device=images.device)
+                post = self._post(out, mask, target)
+        return out, post
+
+    def __call__(self, samples, reflc_points=None, reflc_mat=None, img_name=None, taps=None):
+        """The model's own output dict.  reflc_points / reflc_mat / img_name are accepted as the model accepts them (unused)."""
+        return self._run(samples, None, False, taps=taps)[0]
+
+    forward = __call__
+
+    def predict(self, samples, target_sizes=None, copy=False):
+        """Post-processed results (RESULT_KEYS).  target_sizes (B,2) = (h, w): scale the lines to another size than the
+        un-padded input (the reference passes orig_size for evaluation).  copy=False: see LIFETIME OF OUTPUTS."""
+        res = self._run(samples, target_sizes, True)[1]
+        if copy:
+            res = {k: v.clone() for k, v in res.items()}
+        return res

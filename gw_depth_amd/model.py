@@ -888,8 +888,10 @@ class DensePrediction(nn.Module):
         pad = x.shape[-1] - fc1.weight.shape[-1]            # forward() has already appended the zero channels (in its concat)
         if pad == 0:
             return self.depth_token_fuse(x)
-        h = ops.linear(x, F.pad(fc1.weight, (0, pad, 0, pad)), F.pad(fc1.bias, (0, pad)), ACT_GELU)
-        return ops.linear(h, F.pad(fc2.weight, (0, pad)), fc2.bias)
+        w1 = ops.derived_weight(fc1.weight, pad, lambda: F.pad(fc1.weight, (0, pad, 0, pad)))     # kept by an inference session
+        w2 = ops.derived_weight(fc2.weight, pad, lambda: F.pad(fc2.weight, (0, pad)))
+        h = ops.linear(x, w1, F.pad(fc1.bias, (0, pad)), ACT_GELU)
+        return ops.linear(h, w2, fc2.bias)
 
     _ZERO_BLOCKS = {}
 

@@ -5,6 +5,7 @@ Layout conventions: feature maps are (B, H, W, C) contiguous ("pixel-major"), to
 Master parameters are fp32; with bf16 activations the kernels read a bf16 copy of the weights
 (the flat shadow maintained by the fused optimizer when present, otherwise made on the fly).
 """
+import bisect
 import os
 
 import torch
@@ -27,12 +28,21 @@ class WeightCache:
     copy for the data gradient), refreshed by ONE gwd_weight_prep_batch launch per train step instead of one small
     launch per layer.  engine.TrainStep owns one and brackets each forward/backward with begin_pass() / end_pass();
     outside such a pass (plain ops calls, fp32 runs) every copy is made on the fly as before.  A weight first seen inside a pass is
-    prepared on the fly and joins the table for the next pass."""
+    prepared on the fly and joins the table for the next pass.
 
-    def __init__(self, persistent=()):
+    frozen=True (infer.InferenceSession): the weights do not change between passes.  begin_pass() only activates the cache
+    and launches nothing: a copy is made when its weight is first seen (the first pass) and stays as it is.  refresh() runs
+    the one batch launch and rewrites every copy IN PLACE (a captured HIP graph reads them by address).  A frozen cache also
+    answers for weights that carry a TrainStep's bf16 shadow (see _weight_for): the shadow follows every optimizer step, the
+    frozen copies follow refresh() only."""
+
+    def __init__(self, persistent=(), frozen=False):
+        self.frozen = bool(frozen)
+        self._derived = {}       # frozen mode: (parameter address, tag) -> (maker, tensor), see derived()
         # [start, end) address ranges of PARAMETER storage: only weights living there are cached - a temporary (e.g. a
         # zero-padded copy of a parameter) has a new address every step and must be prepared on the fly
         self.ranges = sorted((int(a), int(b)) for a, b in persistent)
+        self._starts, self._ends, self._merged_from = [], [], -1
         self.jobs = {}           # key -> dict(w, rs, fwd, t)
         self.table = None
         self.n_jobs = self.blocks = 0
@@ -49,13 +59,26 @@ class WeightCache:
         geom = (Np, Cg, Cgp): the zero-padded copies of padded_weight()."""
         if not self.active or not w.is_cuda or w.dtype != torch.float32:
             return None
-        p = w.data_ptr()
-        if not any(a <= p < b for a, b in self.ranges):
+        if not self._persistent(w.data_ptr()):
             return None
         job = self.jobs.get(self._key(w, rs, geom))
         if job is not None and job[kind] is not None:
             return job[kind]        # refreshed by this pass's batch launch, or made earlier in this very pass
         return self._add(w, rs, kind, geom)
+
+    def _persistent(self, p):
+        """p lies in one of the [start, end) ranges.  Bisection over the merged ranges: a session registers one range per
+        parameter and buffer, and every weight of a forward asks."""
+        if self._merged_from != len(self.ranges):
+            merged = []
+            for lo, hi in sorted(self.ranges):
+                if merged and lo <= merged[-1][1]:
+                    merged[-1][1] = max(merged[-1][1], hi)
+                else:
+                    merged.append([lo, hi])
+            self._starts, self._ends, self._merged_from = [m[0] for m in merged], [m[1] for m in merged], len(self.ranges)
+        i = bisect.bisect_right(self._starts, p) - 1
+        return i >= 0 and p < self._ends[i]
 
     def _add(self, w, rs, kind, geom=None):
         key = self._key(w, rs, geom)
@@ -79,7 +102,7 @@ class WeightCache:
         self.dirty = True
         return out
 
-    def begin_pass(self):
+    def _build_table(self):
         if self.dirty and self.jobs:
             recs = (hip.PrepJob * len(self.jobs))()
             b0 = 0
@@ -103,8 +126,15 @@ class WeightCache:
             self.block_job = torch.cat(owners).to(dev)
             self.n_jobs, self.blocks = len(self.jobs), b0
             self.dirty = False
+
+    def _prepare_all(self):
         if self.table is not None:
             _lib().weight_prep_batch(self.table, self.n_jobs, self.blocks, getattr(self, "block_job", None))
+
+    def begin_pass(self):
+        if not self.frozen:
+            self._build_table()
+            self._prepare_all()
         self.active = True
         global _ACTIVE_WEIGHTS
         _ACTIVE_WEIGHTS = self
@@ -113,6 +143,25 @@ class WeightCache:
         global _ACTIVE_WEIGHTS
         self.active = False
         _ACTIVE_WEIGHTS = None
+
+    def derived(self, w, tag, make):
+        """Frozen mode: a weight-shaped tensor the forward derives from parameter w on every call (its zero-padded form), made
+        once and kept at one address, so its kernel-side copy is cached like a parameter's; refresh() remakes it in place."""
+        key = (w.data_ptr(), tag)
+        ent = self._derived.get(key)
+        if ent is None:
+            t = make().detach().contiguous()
+            ent = self._derived[key] = (make, t)
+            self.ranges.append((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()))
+        return ent[1]
+
+    def refresh(self):
+        """Frozen mode: the weights changed (load_state_dict, optimizer steps) - ONE batch launch on the current stream rewrites
+        every copy made so far, in place."""
+        for make, t in self._derived.values():
+            t.copy_(make())
+        self._build_table()
+        self._prepare_all()
 
 
 class ColsumQueue:
@@ -246,8 +295,8 @@ def _weight_for(w, row_scale, dtype, shadow=None):
     if row_scale is None:
         if dtype == torch.float32:
             return w.detach()
-        if shadow is not None and shadow.dtype == dtype:
-            return shadow
+        if shadow is not None and shadow.dtype == dtype and not (_ACTIVE_WEIGHTS is not None and _ACTIVE_WEIGHTS.frozen):
+            return shadow           # a frozen cache answers itself: its copies change at refresh() only, the shadow at every step
     if dtype == torch.bfloat16 and _ACTIVE_WEIGHTS is not None:
         cached = _ACTIVE_WEIGHTS.get(w, row_scale, "fwd")
         if cached is not None:
@@ -256,6 +305,14 @@ def _weight_for(w, row_scale, dtype, shadow=None):
     N, C = w.shape[0], w.shape[-1]
     _lib().weight_prep(w.detach(), row_scale, out, None, N, w.numel() // (N * C), C, hip.F32 if dtype == torch.float32 else hip.BF16)
     return out
+
+
+def derived_weight(w, tag, make):
+    """make(): a weight derived from parameter w inside a forward.  Under a frozen WeightCache (inference) it is made once and
+    kept (WeightCache.derived); otherwise it is made now, as before."""
+    if _ACTIVE_WEIGHTS is not None and _ACTIVE_WEIGHTS.frozen and w.is_cuda and not torch.is_grad_enabled():
+        return _ACTIVE_WEIGHTS.derived(w, tag, make)
+    return make()
 
 
 def _weight_transposed(w, row_scale, dtype):
@@ -1868,3 +1925,40 @@ def point_sample(fmap, coords, nearest=False, frame=None):
             if shift:
                 fmap = torch.roll(fmap, shifts=(-shift, -shift), dims=(1, 2))
     return _PointSampleFn.apply(fmap, coords, 1 if nearest else 0)
+
+
+def dense_postprocess(depth, seg, sizes=None, min_depth=1e-3, max_depth=10.0, with_mm=True, out=None):
+    """Inference post-processing of the dense outputs in one pass (gwd_dense_postprocess): depth (B,1,H,W) / (B,H,W) fp32 or
+    bf16, seg (B,2,H,W) logits in any strides whose two pixel dims collapse (the model's pixel-major view qualifies), sizes
+    (B,2) int32 = un-padded (h, w) or None.  -> (depth fp32 (B,H,W) clamped as engine_glassrgbd.py:249-252, depth_mm uint16
+    or None, labels uint8); padding is 0 / 0 / 255.  out = the three tensors of an earlier call, to be overwritten."""
+    if seg.dim() != 4 or seg.shape[1] != 2:
+        raise ValueError("seg must be (B, 2, H, W) logits, got %s" % (tuple(seg.shape),))
+    B, _, H, W = seg.shape
+    if depth.numel() != B * H * W:
+        raise ValueError("depth %s and seg %s differ" % (tuple(depth.shape), tuple(seg.shape)))
+    depth = depth.reshape(B, H, W).contiguous()
+    if H > 1 and seg.stride(2) != W * seg.stride(3):
+        seg = seg.contiguous()
+    if out is None:
+        out = (torch.empty((B, H, W), dtype=torch.float32, device=depth.device),
+               torch.empty((B, H, W), dtype=torch.uint16, device=depth.device) if with_mm else None,
+               torch.empty((B, H, W), dtype=torch.uint8, device=depth.device))
+    _lib().dense_postprocess(depth, seg, (seg.stride(0), seg.stride(3), seg.stride(1)), sizes, out[0], out[1], out[2], B, H, W,
+                             min_depth, max_depth)
+    return out
+
+
+def line_postprocess(logits, lines, sizes, thresh=0.6):
+    """PostProcess_Line 'prediction' for two classes plus a ranking (gwd_line_postprocess): logits (B,Q,2), lines (B,Q,4|6),
+    sizes (B,2) int32 (h, w) -> scores (B,Q), lines in pixels (B,Q,4), order (B,Q) int32 (score descending, equal scores by
+    lower index), count (B,) int32 (scores > thresh)."""
+    B, Q, ld = lines.shape
+    logits, lines = logits.float().contiguous(), lines.float().contiguous()
+    dev = logits.device
+    scores = torch.empty((B, Q), dtype=torch.float32, device=dev)
+    lines_px = torch.empty((B, Q, 4), dtype=torch.float32, device=dev)
+    order = torch.empty((B, Q), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib().line_postprocess(logits, lines, sizes, scores, lines_px, order, count, B, Q, ld, thresh)
+    return scores, lines_px, order, count

@@ -493,6 +493,30 @@ int gwd_eval_accumulate(const void *pred_depth, const float *gt_depth, const voi
                         double *running, int64_t *confusion, int32_t B, int64_t HW, float min_depth,
                         float max_depth, int32_t depth_dtype, int32_t seg_dtype, void *stream);
 
+/* Inference post-processing of the dense outputs, one streaming pass behind the forward (csrc/postproc.hip).
+ *   depth [B][H][W] (depth_dtype); seg_logits: class c of pixel i of image b at seg_logits[b*seg_sb + i*seg_sp + c*seg_sc]
+ *   (seg_dtype; element strides as for the evaluation entry point above); sizes [B][2] int32 = the un-padded (h, w) of each image
+ *   (images are top-left aligned), NULL = all of H x W.
+ *   depth_out [B][H][W] fp32, depth_mm [B][H][W] uint16 (may be NULL), label [B][H][W] uint8 - every element written.
+ * Inside (h, w): depth_out = the clamp of src/engine_glassrgbd.py:249-252 in that order (< min -> min, > max -> max, +inf -> max,
+ * NaN -> min, hence -inf -> min); depth_mm = rint(depth_out * 1000) saturated to [0, 65535] (the data set's PNG convention,
+ * src/datasets/glassrgbd_norhint.py:273); label = argmax of the two logits by torch.argmax's rules (tie -> 0, a NaN logit is the
+ * maximum, the first one wins).  Outside: depth_out 0, depth_mm 0, label 255 (the ignore value of src/util/metrics.py).
+ * 16-byte accesses when W % 8 == 0, the logits are interleaved (seg_sp 2, seg_sc 1) or planar (seg_sp 1, seg_sc % 8 == 0),
+ * seg_sb % 8 == 0 and all bases are 16-byte aligned; one pixel per thread otherwise.  All shapes are accepted.  One launch. */
+int gwd_dense_postprocess(const void *depth, const void *seg_logits, int64_t seg_sb, int64_t seg_sp, int64_t seg_sc,
+                          const int32_t *sizes, float *depth_out, uint16_t *depth_mm, uint8_t *label, int32_t B, int32_t H,
+                          int32_t W, float min_depth, float max_depth, int32_t depth_dtype, int32_t seg_dtype, void *stream);
+
+/* PostProcess_Line 'prediction' for two classes (src/models/glassrgbd.py:470-477) plus a ranking, one workgroup per image.
+ *   logits [B][Q][2] fp32, lines [B][Q][ld] fp32 with ld 4 or 6, sizes [B][2] int32 (h, w), thresh;
+ *   scores [B][Q] fp32 = softmax probability of class 0 (the labels are all 0), lines_px [B][Q][4] fp32 (16-byte aligned) = the
+ *   first four coordinates times (w, h, w, h), both in query order; order [B][Q] int32 = query indices by score descending, equal
+ *   scores by lower index first (a NaN score ranks above every number, as torch.sort has it); count [B] int32 = scores > thresh.
+ * Q <= 1024, else -2.  One launch, no atomics.                                                                              */
+int gwd_line_postprocess(const float *logits, const float *lines, const int32_t *sizes, float *scores, float *lines_px,
+                         int32_t *order, int32_t *count, int32_t B, int32_t Q, int32_t ld, float thresh, void *stream);
+
 /* PlaneLoss (src/models/glassrgbd.py:385-450, --with_plane_norm_loss) of ONE image, on the device: Sobel normals of the
  * predicted depth (src/models/losses/sobel.py:5-27), the masks of up to P <= 64 line triangles restricted to the valid
  * pixels (the reference: matplotlib.path.Path.contains_points on the host; same crossing test here, exact in integers),
