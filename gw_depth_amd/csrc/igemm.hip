@@ -12,6 +12,7 @@
 // residual add and ReLU / GELU / ELU / sigmoid so a Bottleneck conv writes its activation once.
 #include "common.h"
 #include <cmath>
+#include <utility>
 
 namespace {
 
@@ -394,9 +395,6 @@ __device__ __forceinline__ int xcd_band(int id, int total) {
 // layer runs 0.122 -> 0.108 ms (same-box, 3 runs each).  Gated launches are always lean (the dispatcher sends the rest elsewhere).
 // (ACTK: -1 = any activation, decided at run time, + the pre-activation copy; 0 = none = "lean"; 1 = ReLU, a single v_max - the
 // Bottleneck convolutions.)
-#ifndef GWD_DBG_ZERO
-#define GWD_DBG_ZERO 0      // development ablation builds only (tools/ab_build.sh): bit 0 / 1 = stage the A / B tile from the zero page
-#endif
 template <int BM, int BN, int WM, int WN, int STAGES, int BK = 32>
 struct DmaTileCfg {
     static constexpr int NW = WM * WN;
@@ -427,11 +425,7 @@ struct DmaTileCfg {
 // their A fragments from the same patch at a pixel offset; the transposed gather (stride-1 data gradient) is the same walk with the
 // taps mirrored.  Ring: 2 halo patches (22 KB each: channel block cb + 1 lands while the nine taps of cb compute) + 3 weight tiles.
 struct HaloCfg {
-#if GWD_DBG_ZERO & 128          // timing experiment only (wrong results): ONE halo patch buffer, five weight tiles
-    static constexpr int A_INSTR = 22, A_BYTES = A_INSTR * 1024, B_BYTES = 160 * 64, B_STAGES = 5, A_BUFS = 1;
-#else
     static constexpr int A_INSTR = 22, A_BYTES = A_INSTR * 1024, B_BYTES = 160 * 64, B_STAGES = 3, A_BUFS = 2;
-#endif
     static constexpr int RING = A_BUFS * A_BYTES + B_STAGES * B_BYTES;
 };
 
@@ -569,7 +563,7 @@ __device__ __forceinline__ void dma_tile(const gwd_conv_desc &d, char *smem, con
             ok = ok & a_ok[i];
             if constexpr (TAIL) ok = ok & (u_c0 + a_ck[i] < d.Cin);
             const size_t off = (a_pix[i] + (size_t)(ok ? ih : 0) * d.Wi + (ok ? iw : 0)) * d.Cin + u_c0 + a_ck[i];
-            const char *src = (ok && !(GWD_DBG_ZERO & 1)) ? (const char *)(x + off) : zero;
+            const char *src = ok ? (const char *)(x + off) : zero;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                              (__attribute__((address_space(3))) void *)(sb + (wave * A_IT + i) * 1024), 16, 0, 0);
         }
@@ -578,7 +572,7 @@ __device__ __forceinline__ void dma_tile(const gwd_conv_desc &d, char *smem, con
             if (i < my_b_loads) {                                 // wave-uniform
                 bool bok = b_ok[i];
                 if constexpr (TAIL) bok = bok & (u_c0 + b_ck[i] < d.Cin);
-                const char *src = (bok && !(GWD_DBG_ZERO & 2)) ? b_src[i] + (size_t)((u_kh * d.KW + u_kw) * d.Cin + u_c0) * 2 : zero;
+                const char *src = bok ? b_src[i] + (size_t)((u_kh * d.KW + u_kw) * d.Cin + u_c0) * 2 : zero;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                                  (__attribute__((address_space(3))) void *)(sb + BM * BK * 2 + (wave + i * NW) * 1024), 16, 0, 0);
             }
@@ -648,7 +642,7 @@ __device__ __forceinline__ void dma_tile(const gwd_conv_desc &d, char *smem, con
 #pragma unroll
             for (int i = 0; i < A_IT_H; ++i) {
                 if (wave + 8 * i < HaloCfg::A_INSTR) {            // wave-uniform
-                    const char *src = (ha_ok[i] && !(GWD_DBG_ZERO & 1)) ? ha_src[i] + cb * 64 : zero;
+                    const char *src = ha_ok[i] ? ha_src[i] + cb * 64 : zero;
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                                      (__attribute__((address_space(3))) void *)(ab + (wave + 8 * i) * 1024), 16, 0, 0);
                 }
@@ -660,7 +654,7 @@ __device__ __forceinline__ void dma_tile(const gwd_conv_desc &d, char *smem, con
 #pragma unroll
             for (int i = 0; i < B_IT; ++i) {
                 if (i < my_b_loads) {
-                    const char *src = (b_ok[i] && !(GWD_DBG_ZERO & 2)) ? b_src[i] + (size_t)(i_tap * d.Cin + i_cb * 32) * 2 : zero;
+                    const char *src = b_ok[i] ? b_src[i] + (size_t)(i_tap * d.Cin + i_cb * 32) * 2 : zero;
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                                      (__attribute__((address_space(3))) void *)(sb + (wave + i * NW) * 1024), 16, 0, 0);
                 }
@@ -746,18 +740,14 @@ __device__ __forceinline__ void dma_tile(const gwd_conv_desc &d, char *smem, con
                 case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
                 default: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
             }
-#if !(GWD_DBG_ZERO & 64)
             __builtin_amdgcn_s_barrier();
-#endif
             const int tap = kh * 3 + kw;
             ++a_age;
-#if !(GWD_DBG_ZERO & 32)
             if (tap == 0 && cb + 1 < NCB) {
                 issue_a(cb + 1);
                 a_age = 1;
             }
             if (st + NB - 1 < S) issue_b((st + NB - 1) % NB);
-#endif
             compute_h(cb, GM == 1 ? (2 - kh) * 34 + (2 - kw) : kh * 34 + kw, st % NB);
             if (++kw == 3) {
                 kw = 0;
@@ -1756,12 +1746,6 @@ int check_desc(const gwd_conv_desc *d) {
     return 0;
 }
 
-// Fixed choices (each was an A/B switch while it was being measured; the measurements are in DESIGN.md section 4):
-constexpr bool big_tiles_enabled() { return true; }      // 256-row tiles from M >= 131 072 on
-constexpr bool tail_enabled() { return true; }           // zero-page channel tail for Cin % 32 != 0 (the 80-channel layers)
-constexpr int small_tile_threshold() { return 320; }     // fewer 128 x 128 tiles than this: 64 x 64 tiles
-
-
 // ----------------------------------------------------------------------------------------------
 // long reductions on few rows: K split over the waves of a workgroup
 // ----------------------------------------------------------------------------------------------
@@ -1941,38 +1925,220 @@ __global__ __launch_bounds__(256) void gemm_ksplit_kernel(const gwd_conv_desc d,
     }
 }
 
-constexpr int ksplit_min_k() { return 1024; }
+// ----------------------------------------------------------------------------------------------
+// dispatch: gwd_conv_desc -> plan (pure selection: every threshold, no launch) -> one launcher per kernel family
+// ----------------------------------------------------------------------------------------------
+constexpr int ERR_NOT_BUILT = -9;                         // a plan names a kernel that is not in its family's table (a bug in the selection)
+// value -> template: f(std::integral_constant<int, I>{}) for the first I in [0, N) with match(I)
+template <class Match, class F, int... I>
+int with_index(std::integer_sequence<int, I...>, Match match, F f) {
+    int rc = ERR_NOT_BUILT;
+    (void)((match(I) && ((rc = f(std::integral_constant<int, I>{})), true)) || ...);
+    return rc;
+}
+template <int N, class Match, class F>
+int with_index(Match match, F f) { return with_index(std::make_integer_sequence<int, N>{}, match, f); }
 
-// 1 = launched
-static int launch_ksplit(const gwd_conv_desc *d, hipStream_t s) {
-    const int M = d->B * d->Ho * d->Wo, N = d->Cout, K = d->KH * d->KW * d->Cin;
-    if (ksplit_min_k() <= 0 || K < ksplit_min_k() || d->dtype != GWD_BF16 || !d->zero_page) return 0;
-    if (d->gather == GWD_GATHER_UPSAMPLED || (d->gather == GWD_GATHER_TRANSPOSED && d->stride != 1)) return 0;
-    if ((d->Cin % 32) || (N % 8)) return 0;
-    if (d->gate && d->gate_act == GWD_ACT_GELU) return 0;         // the GELU gate lives in the LDS-DMA tile kernels only
-    const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
-    if (tiles > 256) return 0;                            // one workgroup (128 KiB of LDS) per CU: beyond one round the ordinary tiles win (304 tiles, K = 4 608: 54 -> 58 us; 600 tiles: 17 -> 21 us)
-    constexpr int ST = 4, LDS = 4 * ST * (64 + 64) * 64;  // 128 KiB: one workgroup per CU
-    const bool lean = d->act == GWD_ACT_NONE && !d->z;
-#define KS_LAUNCH(MULT_, LEAN_)                                                                                                    \
-    {                                                                                                                              \
-        static bool attr = false;                                                                                                  \
-        if (!attr) {                                                                                                               \
-            (void)hipFuncSetAttribute((const void *)gemm_ksplit_kernel<ST, MULT_, LEAN_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
-            attr = true;                                                                                                           \
-        }                                                                                                                          \
-        gemm_ksplit_kernel<ST, MULT_, LEAN_><<<(unsigned)tiles, 256, LDS, s>>>(*d, (int)tiles);                                     \
-    }
-    if (d->mult) {
-        if (lean) KS_LAUNCH(true, true) else KS_LAUNCH(true, false)
-    } else {
-        if (lean) KS_LAUNCH(false, true) else KS_LAUNCH(false, false)
-    }
-#undef KS_LAUNCH
-    return 1;
+// Which igemm_dma_kernel instantiations exist: dma_built() over these tiles, and nothing else.
+struct DmaTile {
+    int BM, BN, WM, WN, STAGES, KPB, BK;
+    constexpr bool operator==(const DmaTile &o) const { return BM == o.BM && BN == o.BN && WM == o.WM && WN == o.WN && STAGES == o.STAGES && KPB == o.KPB && BK == o.BK; }
+};
+constexpr DmaTile T256x160{256, 160, 8, 1, 3, 1, 32}, T128x160{128, 160, 4, 1, 3, 1, 32}, T256x128{256, 128, 4, 2, 3, 1, 32}, T128x128{128, 128, 2, 2, 3, 1, 32},
+    T128x64{128, 64, 2, 2, 4, 1, 32}, T128x64_LN{128, 64, 4, 1, 4, 1, 32},      // ConvLn: a wave owns whole rows
+    T128x32{128, 32, 4, 1, 4, 1, 32}, T64x64{64, 64, 2, 2, 4, 1, 32},
+    T64x64_KPB2{64, 64, 2, 2, 6, 2, 32},                 // two 32-channel K tiles per barrier
+    T64x64_BK64{64, 64, 2, 2, 3, 1, 64};                 // 64-channel K tiles
+constexpr DmaTile DMA_TILES[] = {T256x160, T128x160, T256x128, T128x128, T128x64, T128x64_LN, T128x32, T64x64, T64x64_KPB2, T64x64_BK64};
+struct DmaVariant {                                       // igemm_dma_kernel's template parameters by name; GM: 0 plain gather | 1 transposed, stride 1 | 2 anything else
+    DmaTile t;
+    int GM; bool MULT, TAIL; int GATE, ACTK; bool LN, HALO, PAR;
+    constexpr bool operator==(const DmaVariant &o) const { return t == o.t && GM == o.GM && MULT == o.MULT && TAIL == o.TAIL && GATE == o.GATE && ACTK == o.ACTK && LN == o.LN && HALO == o.HALO && PAR == o.PAR; }
+};
+constexpr bool dma_built(const DmaVariant &v) {
+    const bool t256x160 = v.t == T256x160, lean_or_any = v.ACTK == 0 || v.ACTK == -1;
+    if (v.GATE && v.ACTK != 0) return false;             // gated launches are lean
+    if (v.LN)                                             // ConvLn: plain gather, no activation or GELU; the 256 x 160 tile also with a channel tail or as halo tile
+        return v.GM == 0 && !v.MULT && !v.GATE && !v.PAR && (v.ACTK == 0 || v.ACTK == 2) &&
+               (t256x160 ? !(v.TAIL && v.HALO) : ((v.t == T128x64_LN || v.t == T128x32) && !v.TAIL && !v.HALO));
+    if (v.t == T128x64_LN) return false;
+    if (v.MULT) return v.t == T64x64 && v.GM == 0 && !v.TAIL && !v.GATE && !v.HALO && !v.PAR && v.ACTK != 2;
+    if (v.TAIL) return (t256x160 || v.t == T256x128) && v.GM <= 1 && !v.GATE && !v.HALO && !v.PAR && lean_or_any;
+    if (v.HALO) return t256x160 && v.GM <= 1 && !v.GATE && !v.PAR && lean_or_any;
+    if (v.PAR) return (v.t == T128x128 || v.t == T64x64_BK64) && v.GM == 2 && v.GATE <= 1 && v.ACTK == 0;
+    if (v.t.BN % 160 == 0) return !v.GATE && lean_or_any;    // 160-wide tiles never carry a gate or a compile-time ReLU / GELU
+    return true;
+}
+struct DmaTable { DmaVariant v[256]; int n; };
+constexpr DmaTable dma_table() {
+    DmaTable tab{};
+    for (const DmaTile &t : DMA_TILES)
+        for (int gm = 0; gm < 3; ++gm)
+            for (int flags = 0; flags < 32; ++flags)
+                for (int gate = 0; gate < 3; ++gate)
+                    for (int actk = -1; actk < 3; ++actk) {
+                        const DmaVariant v{t, gm, (flags & 1) != 0, (flags & 2) != 0, gate, actk, (flags & 4) != 0, (flags & 8) != 0, (flags & 16) != 0};
+                        if (dma_built(v)) tab.v[tab.n++] = v;
+                    }
+    return tab;
+}
+constexpr DmaTable DMA_TABLE = dma_table();
+static_assert(DMA_TABLE.n == 167, "adding or dropping an igemm_dma_kernel instantiation is a decision of its own");
+
+// register-staged forward kernels (fp32, and bf16 shapes the LDS-DMA route does not take), each for both types
+struct StagedVariant {
+    int BM, BN, WM, WN; bool MULT;
+    constexpr bool operator==(const StagedVariant &o) const { return BM == o.BM && BN == o.BN && WM == o.WM && WN == o.WN && MULT == o.MULT; }
+};
+constexpr StagedVariant STAGED_VARIANTS[] = {{64, 64, 2, 2, true}, {128, 160, 4, 1, false}, {64, 64, 2, 2, false}, {128, 128, 2, 2, false}, {128, 64, 2, 2, false}, {128, 32, 4, 1, false}};
+constexpr int N_STAGED = sizeof(STAGED_VARIANTS) / sizeof(STAGED_VARIANTS[0]);
+
+enum class ConvFamily { KSPLIT, DMA, STAGED, DECLINED };
+struct ConvPlan {
+    ConvFamily family;
+    DmaVariant dma;                                       // DMA; KSPLIT reads MULT and ACTK == 0 (lean)
+    StagedVariant staged;                                 // STAGED
+    unsigned grid[2], block, lds; int rc;                 // lds: dynamic LDS bytes.  DECLINED: rc = what the entry point returns
+};
+
+constexpr int BIG_TILE_MIN_M = 256 * 512;                 // 256-row tiles from here on: >= 2 workgroups per CU
+constexpr int SMALL_TILE_MAX_T128 = 320;                  // fewer 128 x 128 tiles than this: 64 x 64 tiles
+constexpr int KSPLIT_MIN_K = 1024;
+constexpr int KSPLIT_STAGES = 4, KSPLIT_LDS = 4 * KSPLIT_STAGES * (64 + 64) * 64;      // 128 KiB: one workgroup per CU
+
+// 3x3 / stride 1 / pad 1 on a map of whole 8 x 32 pixel patches, whole 32-channel blocks: the halo-patch variant of the 256 x 160 tile
+constexpr bool halo_ok(const gwd_conv_desc &d) {
+    return d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Hi == d.Ho && d.Wi == d.Wo && (d.Wo % 32) == 0 && (d.Ho % 8) == 0 &&
+           (d.Cin % 32) == 0 && (d.Cout % 160) == 0 && (d.gather == GWD_GATHER_CONV || d.gather == GWD_GATHER_TRANSPOSED);
+}
+// data gradient of a 3x3 / stride 2 / pad 1 convolution onto a map of exactly twice the size: the parity-class variant
+constexpr bool par_ok(const gwd_conv_desc &d) {
+    return d.gather == GWD_GATHER_TRANSPOSED && d.stride == 2 && d.KH == 3 && d.KW == 3 && d.pad == 1 && d.Ho == 2 * d.Hi && d.Wo == 2 * d.Wi && (d.Cin % 32) == 0;
 }
 
-static bool dma_enabled() {
+ConvPlan dma_plan(const DmaTile &t, int gm, unsigned tiles) {      // plain variant of the tile; the caller sets what differs, by name
+    return {ConvFamily::DMA, {t, gm, false, false, 0, -1, false, false, false}, {}, {tiles, 1}, unsigned(t.WM * t.WN * 64), 0, 0};
+}
+ConvPlan staged_plan(const StagedVariant &v, unsigned gx, unsigned gy) { return {ConvFamily::STAGED, {}, v, {gx, gy}, 256, 0, 0}; }
+ConvPlan declined(int rc) { return {ConvFamily::DECLINED, {}, {}, {}, 0, 0, rc}; }
+
+// gwd_conv_desc.ln_mean != NULL: convolution with the ConvLn epilogue (dma_tile<..., LN>), or -4 = no fused kernel for the shape (the
+// caller runs convolution and LayerNorm apart)
+ConvPlan plan_convln(const gwd_conv_desc &d, bool dma_on) {
+    const int M = d.B * d.Ho * d.Wo, N = d.Cout;
+    if (d.dtype != GWD_BF16 || !dma_on || !d.zero_page || !d.ln_rstd || !d.scale || !d.shift || d.mult || d.gate) return declined(-4);
+    if (d.gather != GWD_GATHER_CONV || (d.act != GWD_ACT_NONE && d.act != GWD_ACT_GELU) || d.act_scale != 1.0f) return declined(-4);
+    if (d.ln_C <= 0 || d.ln_C > N || (N % 8) || (d.Cin % 8)) return declined(-4);
+    const bool tail = (d.Cin % 32) != 0;
+    if (tail && d.Cin < 32) return declined(-4);
+    ConvPlan p;
+    if (N == 160) {
+        // smaller maps (the PSP branches on pooled maps) run 128 x 160 tiles at two waves per SIMD: the longer epilogue costs more than
+        // the separate LayerNorm launch there (8x30x40: 45.3 us as two launches, 49.5 us fused) - not fused
+        if (M < BIG_TILE_MIN_M) return declined(-4);
+        p = dma_plan(T256x160, 0, (M + 255) / 256);
+        p.dma.TAIL = tail;
+        p.dma.HALO = !tail && halo_ok(d);
+    } else if (tail || N > 64) {
+        return declined(-4);
+    } else {
+        p = dma_plan(N <= 32 ? T128x32 : T128x64_LN, 0, (M + 127) / 128);
+    }
+    p.dma.LN = true;
+    p.dma.ACTK = d.act == GWD_ACT_GELU ? 2 : 0;
+    return p;
+}
+
+// forward / data gradient.  dma_on: GWD_IGEMM_DMA != 0
+ConvPlan plan_forward(const gwd_conv_desc &d, bool dma_on) {
+    const int M = d.B * d.Ho * d.Wo, N = d.Cout, K = d.KH * d.KW * d.Cin;
+    const bool bf16 = d.dtype == GWD_BF16, dma = bf16 && dma_on && d.zero_page;
+    const unsigned gm = (M + 127) / 128, gm2 = (M + 255) / 256;
+    const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
+    const unsigned t64 = (unsigned)tiles64;              // 64 x 64 tiles
+    if (d.ln_mean) return plan_convln(d, dma_on);
+    const int gate = !d.gate ? 0 : (d.gate_act == GWD_ACT_GELU ? 2 : 1);
+    // K split over the waves of a workgroup (gemm_ksplit_kernel); the GELU gate lives in the LDS-DMA tile kernels only
+    if (bf16 && d.zero_page && K >= KSPLIT_MIN_K && d.gather != GWD_GATHER_UPSAMPLED && !(d.gather == GWD_GATHER_TRANSPOSED && d.stride != 1) &&
+        (d.Cin % 32) == 0 && (N % 8) == 0 && gate != 2 &&
+        tiles64 <= 256) {                                    // one workgroup (128 KiB of LDS) per CU: beyond one round the ordinary tiles win (304 tiles, K = 4 608: 54 -> 58 us; 600 tiles: 17 -> 21 us)
+        ConvPlan p = {ConvFamily::KSPLIT, {}, {}, {t64, 1}, 256, KSPLIT_LDS, 0};
+        p.dma.MULT = d.mult != nullptr;
+        p.dma.ACTK = (d.act == GWD_ACT_NONE && !d.z) ? 0 : -1;
+        return p;
+    }
+    if (d.mult) {
+        // element-wise multiplier in the epilogue (dropout + skip of the DETR sub-layers: GEMMs with M <= a few thousand rows):
+        // dedicated instantiations of the 64x64 tiles, so that the multiplier path costs the other kernels nothing
+        if (dma && (d.Cin % 32) == 0 && (N % 8) == 0 && d.gather == GWD_GATHER_CONV) {
+            ConvPlan p = dma_plan(T64x64, 0, t64);
+            p.dma.MULT = true;
+            p.dma.ACTK = d.z ? -1 : (d.act == GWD_ACT_NONE ? 0 : (d.act == GWD_ACT_RELU ? 1 : -1));
+            return p;
+        }
+        return staged_plan({64, 64, 2, 2, true}, (M + 63) / 64, (N + 63) / 64);
+    }
+    // compile-time activation: 2 GELU | 1 ReLU | 0 none ("lean") | -1 decided at run time, + the pre-activation copy
+    const int actk = d.act == GWD_ACT_GELU ? 2 : (d.z ? -1 : (d.act == GWD_ACT_NONE ? 0 : (d.act == GWD_ACT_RELU ? 1 : -1)));
+    const bool lean = actk == 0;
+    const int gmk = d.gather == GWD_GATHER_CONV ? 0 : ((d.gather == GWD_GATHER_TRANSPOSED && d.stride == 1) ? 1 : 2);
+    const bool big = M >= BIG_TILE_MIN_M;
+    // Cin = 8 (mod 32) multiples such as the 80-channel pyramid: the LDS-DMA kernels with a zero-page channel tail (big maps, the two
+    // hot tile shapes, plain and stride-1 transposed gathers) instead of the register-staged kernel (112-166 us per launch)
+    if (dma && !gate && (d.Cin % 32) != 0 && (d.Cin % 8) == 0 && d.Cin > 32 && (N % 8) == 0 && big && gmk <= 1 && N > 64) {
+        ConvPlan p = N % 160 == 0 ? dma_plan(T256x160, gmk, gm2 * (N / 160)) : dma_plan(T256x128, gmk, gm2 * ((N + 127) / 128));
+        p.dma.TAIL = true;
+        p.dma.ACTK = lean ? 0 : -1;
+        return p;
+    }
+    // a gate on a 160-wide layer or together with an activation / a pre-activation copy (none in the model) goes to the
+    // register-staged kernel below: the 160-wide tiles stay gate-free, the gated variants lean
+    if (dma && (d.Cin % 32) == 0 && (N % 8) == 0 && !(gate && (N % 160 == 0 || !lean))) {
+        // 64-channel K tiles (whole 128-byte lines per staged row piece) where every tap is a whole number of them; for the 64 x 64
+        // tiles only (128 x 64 and 128 x 128 with two stages: no gain, measured)
+        const bool bk64 = (d.Cin % 64) == 0;
+        // otherwise two 32-channel K tiles per barrier for them (needs an even number of K tiles)
+        const bool kpb2 = ((d.KH * d.KW * (d.Cin / 32)) % 2) == 0;
+        ConvPlan p;
+        if (gmk == 2 && par_ok(d) && N > 64 && lean && gate != 2) {
+            // stride-2 3x3 data gradient by parity class (dma_tile<..., PAR>): 4 x ceil(M / 4 / BM) row tiles
+            const int mq = M / 4;
+            const unsigned t128 = 4u * ((mq + 127) / 128) * ((N + 127) / 128);
+            p = (t128 >= 512 || !bk64) ? dma_plan(T128x128, 2, t128) : dma_plan(T64x64_BK64, 2, 4u * ((mq + 63) / 64) * ((N + 63) / 64));
+            p.dma.PAR = true;
+        } else if (N % 160 == 0) {
+            p = big ? dma_plan(T256x160, gmk, gm2 * (N / 160)) : dma_plan(T128x160, gmk, gm * (N / 160));
+            p.dma.HALO = big && gmk <= 1 && halo_ok(d);
+        } else if (N > 64) {
+            const unsigned t128 = gm * ((N + 127) / 128);
+            if (big) p = dma_plan(T256x128, gmk, gm2 * ((N + 127) / 128));
+            else if ((int)t128 >= SMALL_TILE_MAX_T128) p = dma_plan(T128x128, gmk, t128);
+            // fewer 128x128 tiles than CUs: quarter tiles put four times as many workgroups on the chip
+            else p = dma_plan(bk64 ? T64x64_BK64 : (kpb2 ? T64x64_KPB2 : T64x64), gmk, t64);
+        } else if (N > 32) {
+            // fewer 128-row tiles than two per CU: 64-row tiles (three workgroups per CU fit) run the map in one round instead of
+            // a round and a tail (conv3x3 64 -> 64 @ 8x60x80: 300 workgroups of 128 x 64 = 1.17 rounds)
+            if (bk64 && gm < 512 && d.KH * d.KW > 1) p = dma_plan(T64x64_BK64, gmk, (M + 63) / 64);      // same box: 18 -> 12 us, step -0.1 ms; 1x1: no gain
+            else p = dma_plan(T128x64, gmk, gm);
+        } else {
+            p = dma_plan(T128x32, gmk, gm);
+        }
+        p.dma.GATE = gate;
+        p.dma.ACTK = (p.dma.t.BN % 160 == 0 && actk > 0) ? -1 : actk;      // the 160-wide tiles decide ReLU / GELU at run time
+        return p;
+    }
+    if (gate == 2) return declined(-4);                   // GELU gate: LDS-DMA tile kernels only; the caller applies it in a pass of its own
+    // register-staged kernels.  Fewer than two tiles per CU (the 60/120-channel pyramid at 1/8 resolution: 300 tiles of 128 rows = one
+    // full round plus a tail round of 44): quarter tiles give four times as many workgroups
+    const bool quarter = N > 32 && gm * ((N + 127) / 128) < 512;
+    if (N % 160 == 0) return staged_plan({128, 160, 4, 1, false}, gm, N / 160);      // 160 / 320 channel pyramids: exact tiles, no padded columns
+    if (quarter) return staged_plan({64, 64, 2, 2, false}, (M + 63) / 64, (N + 63) / 64);
+    if (N > 64) return staged_plan({128, 128, 2, 2, false}, gm, (N + 127) / 128);
+    if (N > 32) return staged_plan({128, 64, 2, 2, false}, gm, 1);
+    return staged_plan({128, 32, 4, 1, false}, gm, 1);
+}
+
+bool dma_enabled() {
     static int v = -1;
     if (v < 0) {
         const char *e = getenv("GWD_IGEMM_DMA");
@@ -1981,243 +2147,68 @@ static bool dma_enabled() {
     return v == 1;
 }
 
-// gwd_conv_desc.ln_mean != NULL: convolution with the ConvLn epilogue (dma_tile<..., LN>).  0 = launched, -4 = no fused kernel for the shape.
-// 3x3 / stride 1 / pad 1 on a map of whole 8 x 32 pixel patches, whole 32-channel blocks: the halo-patch variant of the 256 x 160 tile
-static bool halo_ok(const gwd_conv_desc *d) {
-#ifdef GWD_NO_HALO
-    return false;
-#endif
-    return d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->Hi == d->Ho && d->Wi == d->Wo && (d->Wo % 32) == 0 && (d->Ho % 8) == 0 &&
-           (d->Cin % 32) == 0 && (d->Cout % 160) == 0 && (d->gather == GWD_GATHER_CONV || d->gather == GWD_GATHER_TRANSPOSED);
+int launch_dma(const ConvPlan &p, const gwd_conv_desc *d, hipStream_t s) {
+    return with_index<DMA_TABLE.n>([&](int i) { return DMA_TABLE.v[i] == p.dma; }, [&](auto I) {
+        constexpr DmaVariant v = DMA_TABLE.v[decltype(I)::value];
+        igemm_dma_kernel<v.t.BM, v.t.BN, v.t.WM, v.t.WN, v.t.STAGES, v.GM, v.MULT, v.TAIL, v.GATE, v.ACTK, v.LN, v.t.KPB, v.t.BK, v.HALO, v.PAR>
+            <<<p.grid[0], p.block, p.lds, s>>>(*d, 0, (int)p.grid[0]);
+        return 0;
+    });
 }
-
-// data gradient of a 3x3 / stride 2 / pad 1 convolution onto a map of exactly twice the size: the parity-class variant
-static bool par_ok(const gwd_conv_desc *d) {
-#ifdef GWD_NO_PAR
-    return false;
-#endif
-    return d->gather == GWD_GATHER_TRANSPOSED && d->stride == 2 && d->KH == 3 && d->KW == 3 && d->pad == 1 && d->Ho == 2 * d->Hi && d->Wo == 2 * d->Wi &&
-           (d->Cin % 32) == 0;
-}
-
-static int launch_convln(const gwd_conv_desc *d, hipStream_t s) {
-    const int M = d->B * d->Ho * d->Wo, N = d->Cout;
-    if (d->dtype != GWD_BF16 || !dma_enabled() || !d->zero_page || !d->ln_rstd || !d->scale || !d->shift || d->mult || d->gate) return -4;
-    if (d->gather != GWD_GATHER_CONV || (d->act != GWD_ACT_NONE && d->act != GWD_ACT_GELU) || d->act_scale != 1.0f) return -4;
-    if (d->ln_C <= 0 || d->ln_C > N || (N % 8) || (d->Cin % 8)) return -4;
-    const bool tail = (d->Cin % 32) != 0;
-    if (tail && d->Cin < 32) return -4;
-    const bool gelu = d->act == GWD_ACT_GELU;
-#define LN_LAUNCH(BM_, BN_, WM_, WN_, ST_, TAIL_, GRID)                                                                           \
-    {                                                                                                                             \
-        const dim3 g_(GRID);                                                                                                      \
-        if (gelu) igemm_dma_kernel<BM_, BN_, WM_, WN_, ST_, 0, false, TAIL_, false, 2, true><<<g_, WM_ * WN_ * 64, 0, s>>>(*d, 0, (int)g_.x); \
-        else igemm_dma_kernel<BM_, BN_, WM_, WN_, ST_, 0, false, TAIL_, false, 0, true><<<g_, WM_ * WN_ * 64, 0, s>>>(*d, 0, (int)g_.x);      \
-    }
-    if (N == 160) {
-        if (big_tiles_enabled() && M >= 256 * 512) {
-            if (tail) LN_LAUNCH(256, 160, 8, 1, 3, true, (M + 255) / 256)
-            else if (halo_ok(d)) {
-                const dim3 g_((M + 255) / 256);
-                if (gelu) igemm_dma_kernel<256, 160, 8, 1, 3, 0, false, false, false, 2, true, 1, 32, true><<<g_, 512, 0, s>>>(*d, 0, (int)g_.x);
-                else igemm_dma_kernel<256, 160, 8, 1, 3, 0, false, false, false, 0, true, 1, 32, true><<<g_, 512, 0, s>>>(*d, 0, (int)g_.x);
-            } else LN_LAUNCH(256, 160, 8, 1, 3, false, (M + 255) / 256)
-            return 0;
+int launch_ksplit(const ConvPlan &p, const gwd_conv_desc *d, hipStream_t s) {
+    return with_index<4>([&](int i) { return i == (p.dma.MULT ? 1 : 0) + (p.dma.ACTK == 0 ? 2 : 0); }, [&](auto I) {
+        constexpr bool MULT = (decltype(I)::value & 1) != 0, LEAN = (decltype(I)::value & 2) != 0;
+        static bool attr = false;
+        if (!attr) {
+            (void)hipFuncSetAttribute((const void *)gemm_ksplit_kernel<KSPLIT_STAGES, MULT, LEAN>, hipFuncAttributeMaxDynamicSharedMemorySize, KSPLIT_LDS);
+            attr = true;
         }
-        // smaller maps (the PSP branches on pooled maps) run 128 x 160 tiles at two waves per SIMD: the longer epilogue costs more than
-        // the separate LayerNorm launch there (8x30x40: 45.3 us as two launches, 49.5 us fused) - not fused
-        return -4;
-    }
-    if (tail) return -4;
-    if (N <= 32) LN_LAUNCH(128, 32, 4, 1, 4, false, (M + 127) / 128)
-    else if (N <= 64) LN_LAUNCH(128, 64, 4, 1, 4, false, (M + 127) / 128)
-    else return -4;
-#undef LN_LAUNCH
-    return 0;
+        gemm_ksplit_kernel<KSPLIT_STAGES, MULT, LEAN><<<p.grid[0], p.block, p.lds, s>>>(*d, (int)p.grid[0]);
+        return 0;
+    });
 }
-
 template <typename T>
+int launch_staged(const ConvPlan &p, const gwd_conv_desc *d, hipStream_t s) {
+    return with_index<N_STAGED>([&](int i) { return STAGED_VARIANTS[i] == p.staged; }, [&](auto I) {
+        constexpr StagedVariant v = STAGED_VARIANTS[decltype(I)::value];
+        igemm_fwd_kernel<T, v.BM, v.BN, v.WM, v.WN, Cfg<T>::BK, v.MULT><<<dim3(p.grid[0], p.grid[1]), p.block, 0, s>>>(*d);
+        return 0;
+    });
+}
 int launch_fwd(const gwd_conv_desc *d, hipStream_t s) {
-    const int M = d->B * d->Ho * d->Wo, N = d->Cout;
-    constexpr int BK = Cfg<T>::BK;
-    const unsigned gm = (M + 127) / 128;
-    if (d->ln_mean) {                         // ConvLn epilogue: a fused kernel or -4 (the caller runs convolution and LayerNorm apart)
-        const int rc = launch_convln(d, s);
-        if (rc) return rc;
-        GWD_CHECK_LAUNCH();
-        return 0;
-    }
-    if constexpr (sizeof(T) == 2) {
-        if (launch_ksplit(d, s)) {
-            GWD_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-    if (d->mult) {
-        // element-wise multiplier in the epilogue (dropout + skip of the DETR sub-layers: GEMMs with M <= a few thousand rows):
-        // dedicated instantiations of the 64x64 tiles, so that the multiplier path costs the other kernels nothing
-        if constexpr (sizeof(T) == 2) {
-            if (dma_enabled() && d->zero_page && (d->Cin % 32) == 0 && (N % 8) == 0 && d->gather == GWD_GATHER_CONV) {
-                const dim3 g(((M + 63) / 64) * ((N + 63) / 64));
-                if (!d->z && d->act == GWD_ACT_NONE) igemm_dma_kernel<64, 64, 2, 2, 4, 0, true, false, false, 0><<<g, 256, 0, s>>>(*d, 0, (int)g.x);
-                else if (!d->z && d->act == GWD_ACT_RELU) igemm_dma_kernel<64, 64, 2, 2, 4, 0, true, false, false, 1><<<g, 256, 0, s>>>(*d, 0, (int)g.x);
-                else igemm_dma_kernel<64, 64, 2, 2, 4, 0, true><<<g, 256, 0, s>>>(*d, 0, (int)g.x);
-                GWD_CHECK_LAUNCH();
-                return 0;
-            }
-        }
-        igemm_fwd_kernel<T, 64, 64, 2, 2, BK, true><<<dim3((M + 63) / 64, (N + 63) / 64), 256, 0, s>>>(*d);
-        GWD_CHECK_LAUNCH();
-        return 0;
-    }
-    if constexpr (sizeof(T) == 2) {
-        // Cin = 8 (mod 32) multiples such as the 80-channel pyramid: the LDS-DMA kernels with a zero-page channel tail (big maps, the two
-        // hot tile shapes, plain and stride-1 transposed gathers) instead of the register-staged kernel (112-166 us per launch)
-        const int actk = d->act == GWD_ACT_GELU ? 2 : (d->z ? -1 : (d->act == GWD_ACT_NONE ? 0 : (d->act == GWD_ACT_RELU ? 1 : -1)));
-        const bool lean = actk == 0;
-        if (dma_enabled() && tail_enabled() && !d->gate && d->zero_page && (d->Cin % 32) != 0 && (d->Cin % 8) == 0 && d->Cin > 32 && (N % 8) == 0 && M >= 256 * 512 &&
-            (d->gather == GWD_GATHER_CONV || (d->gather == GWD_GATHER_TRANSPOSED && d->stride == 1))) {
-            const bool tr = d->gather != GWD_GATHER_CONV;
-            const unsigned gm2 = (M + 255) / 256;
-            if (N % 160 == 0) {
-                const dim3 g(gm2 * (N / 160));
-                if (lean) {
-                    if (tr) igemm_dma_kernel<256, 160, 8, 1, 3, 1, false, true, false, 0><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                    else igemm_dma_kernel<256, 160, 8, 1, 3, 0, false, true, false, 0><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                } else if (tr) igemm_dma_kernel<256, 160, 8, 1, 3, 1, false, true><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                else igemm_dma_kernel<256, 160, 8, 1, 3, 0, false, true><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                GWD_CHECK_LAUNCH();
-                return 0;
-            }
-            if (N > 64) {
-                const dim3 g(gm2 * ((N + 127) / 128));
-                if (lean) {
-                    if (tr) igemm_dma_kernel<256, 128, 4, 2, 3, 1, false, true, false, 0><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                    else igemm_dma_kernel<256, 128, 4, 2, 3, 0, false, true, false, 0><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                } else if (tr) igemm_dma_kernel<256, 128, 4, 2, 3, 1, false, true><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                else igemm_dma_kernel<256, 128, 4, 2, 3, 0, false, true><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                GWD_CHECK_LAUNCH();
-                return 0;
-            }
-        }
-        // a gate on a 160-wide layer or together with an activation / a pre-activation copy (none in the model) goes to the
-        // register-staged kernel below: the 160-wide tiles stay gate-free, the gated variants lean
-        if (dma_enabled() && d->zero_page && (d->Cin % 32) == 0 && (N % 8) == 0 && !(d->gate && (N % 160 == 0 || !lean))) {
-            const int gmk = d->gather == GWD_GATHER_CONV ? 0 : ((d->gather == GWD_GATHER_TRANSPOSED && d->stride == 1) ? 1 : 2);
-#define DMA_LAUNCH_G(BM_, BN_, WM_, WN_, ST_, GRID, G_, L_, KPB_)                                              \
-    switch (gmk) {                                                                                              \
-        case 0: igemm_dma_kernel<BM_, BN_, WM_, WN_, ST_, 0, false, false, G_, L_, false, KPB_><<<GRID, WM_ * WN_ * 64, 0, s>>>(*d, 0, (int)(GRID).x); break;   \
-        case 1: igemm_dma_kernel<BM_, BN_, WM_, WN_, ST_, 1, false, false, G_, L_, false, KPB_><<<GRID, WM_ * WN_ * 64, 0, s>>>(*d, 0, (int)(GRID).x); break;   \
-        default: igemm_dma_kernel<BM_, BN_, WM_, WN_, ST_, 2, false, false, G_, L_, false, KPB_><<<GRID, WM_ * WN_ * 64, 0, s>>>(*d, 0, (int)(GRID).x); break;  \
-    }
-#define DMA_LAUNCH_K(BM_, BN_, WM_, WN_, ST_, GRID, KPB_)                                                      \
-    if (BN_ % 160 != 0 && d->gate && d->gate_act == GWD_ACT_GELU) { DMA_LAUNCH_G(BM_, BN_, WM_, WN_, ST_, GRID, (BN_ % 160 != 0 ? 2 : 0), 0, KPB_) }   \
-    else if (BN_ % 160 != 0 && d->gate) { DMA_LAUNCH_G(BM_, BN_, WM_, WN_, ST_, GRID, (BN_ % 160 != 0 ? 1 : 0), 0, KPB_) }   \
-    else if (actk == 0) { DMA_LAUNCH_G(BM_, BN_, WM_, WN_, ST_, GRID, 0, 0, KPB_) }                         \
-    else if (actk == 1 && BN_ % 160 != 0) { DMA_LAUNCH_G(BM_, BN_, WM_, WN_, ST_, GRID, 0, (BN_ % 160 != 0 ? 1 : -1), KPB_) } \
-    else if (actk == 2 && BN_ % 160 != 0) { DMA_LAUNCH_G(BM_, BN_, WM_, WN_, ST_, GRID, 0, (BN_ % 160 != 0 ? 2 : -1), KPB_) } \
-    else { DMA_LAUNCH_G(BM_, BN_, WM_, WN_, ST_, GRID, 0, -1, KPB_) }
-#define DMA_LAUNCH(BM_, BN_, WM_, WN_, ST_, GRID) DMA_LAUNCH_K(BM_, BN_, WM_, WN_, ST_, GRID, 1)
-#define DMA_LAUNCH_G64(BM_, BN_, WM_, WN_, ST_, GRID, G_, L_)                                                   \
-    switch (gmk) {                                                                                              \
-        case 0: igemm_dma_kernel<BM_, BN_, WM_, WN_, ST_, 0, false, false, G_, L_, false, 1, 64><<<GRID, WM_ * WN_ * 64, 0, s>>>(*d, 0, (int)(GRID).x); break;   \
-        case 1: igemm_dma_kernel<BM_, BN_, WM_, WN_, ST_, 1, false, false, G_, L_, false, 1, 64><<<GRID, WM_ * WN_ * 64, 0, s>>>(*d, 0, (int)(GRID).x); break;   \
-        default: igemm_dma_kernel<BM_, BN_, WM_, WN_, ST_, 2, false, false, G_, L_, false, 1, 64><<<GRID, WM_ * WN_ * 64, 0, s>>>(*d, 0, (int)(GRID).x); break;  \
-    }
-#define DMA_LAUNCH_64(BM_, BN_, WM_, WN_, ST_, GRID)                                                           \
-    if (d->gate && d->gate_act == GWD_ACT_GELU) { DMA_LAUNCH_G64(BM_, BN_, WM_, WN_, ST_, GRID, 2, 0) }          \
-    else if (d->gate) { DMA_LAUNCH_G64(BM_, BN_, WM_, WN_, ST_, GRID, 1, 0) }                                   \
-    else if (actk == 0) { DMA_LAUNCH_G64(BM_, BN_, WM_, WN_, ST_, GRID, 0, 0) }                             \
-    else if (actk == 1) { DMA_LAUNCH_G64(BM_, BN_, WM_, WN_, ST_, GRID, 0, 1) }                             \
-    else if (actk == 2) { DMA_LAUNCH_G64(BM_, BN_, WM_, WN_, ST_, GRID, 0, 2) }                             \
-    else { DMA_LAUNCH_G64(BM_, BN_, WM_, WN_, ST_, GRID, 0, -1) }
-            // 64-channel K tiles (whole 128-byte lines per staged row piece) where every tap is a whole number of them; for the 64 x 64
-            // tiles only (128 x 64 and 128 x 128 with two stages: no gain, measured)
-            const bool bk64 = (d->Cin % 64) == 0;
-            // otherwise two 32-channel K tiles per barrier for them (needs an even number of K tiles)
-            const bool kpb2 = ((d->KH * d->KW * (d->Cin / 32)) % 2) == 0;
-            const bool big = big_tiles_enabled() && M >= 256 * 512;      // >= 2 workgroups per CU with 256-row tiles
-            const unsigned gm2 = (M + 255) / 256;
-            if (gmk == 2 && par_ok(d) && N > 64 && lean && !(d->gate && d->gate_act == GWD_ACT_GELU)) {
-                // stride-2 3x3 data gradient by parity class (dma_tile<..., PAR>): 4 x ceil(M / 4 / BM) row tiles
-                const int mq = M / 4;
-                const unsigned t128 = 4u * ((mq + 127) / 128) * ((N + 127) / 128);
-                if (t128 >= 512 || !bk64) {
-                    const dim3 g(t128);
-                    if (d->gate) igemm_dma_kernel<128, 128, 2, 2, 3, 2, false, false, true, 0, false, 1, 32, false, true><<<g, 256, 0, s>>>(*d, 0, (int)g.x);
-                    else igemm_dma_kernel<128, 128, 2, 2, 3, 2, false, false, false, 0, false, 1, 32, false, true><<<g, 256, 0, s>>>(*d, 0, (int)g.x);
-                } else {
-                    const dim3 g(4u * ((mq + 63) / 64) * ((N + 63) / 64));
-                    if (d->gate) igemm_dma_kernel<64, 64, 2, 2, 3, 2, false, false, true, 0, false, 1, 64, false, true><<<g, 256, 0, s>>>(*d, 0, (int)g.x);
-                    else igemm_dma_kernel<64, 64, 2, 2, 3, 2, false, false, false, 0, false, 1, 64, false, true><<<g, 256, 0, s>>>(*d, 0, (int)g.x);
-                }
-            } else if (N % 160 == 0) {
-                if (big && gmk <= 1 && halo_ok(d)) {
-                    const dim3 g(gm2 * (N / 160));
-                    if (actk == 0) {
-                        if (gmk == 0) igemm_dma_kernel<256, 160, 8, 1, 3, 0, false, false, false, 0, false, 1, 32, true><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                        else igemm_dma_kernel<256, 160, 8, 1, 3, 1, false, false, false, 0, false, 1, 32, true><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                    } else {
-                        if (gmk == 0) igemm_dma_kernel<256, 160, 8, 1, 3, 0, false, false, false, -1, false, 1, 32, true><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                        else igemm_dma_kernel<256, 160, 8, 1, 3, 1, false, false, false, -1, false, 1, 32, true><<<g, 512, 0, s>>>(*d, 0, (int)g.x);
-                    }
-                } else if (big) { DMA_LAUNCH(256, 160, 8, 1, 3, dim3(gm2 * (N / 160))) } else { DMA_LAUNCH(128, 160, 4, 1, 3, dim3(gm * (N / 160))) }
-            } else if (N > 64) {
-                const unsigned t128 = gm * ((N + 127) / 128);
-                const int small_thr = small_tile_threshold();
-                if (big) { DMA_LAUNCH(256, 128, 4, 2, 3, dim3(gm2 * ((N + 127) / 128))) }
-                else if ((int)t128 < small_thr) {
-                    // fewer 128x128 tiles than CUs: quarter tiles put four times as many workgroups on the chip
-                    if (bk64) { DMA_LAUNCH_64(64, 64, 2, 2, 3, dim3(((M + 63) / 64) * ((N + 63) / 64))) }
-                    else if (kpb2) { DMA_LAUNCH_K(64, 64, 2, 2, 6, dim3(((M + 63) / 64) * ((N + 63) / 64)), 2) }
-                    else { DMA_LAUNCH(64, 64, 2, 2, 4, dim3(((M + 63) / 64) * ((N + 63) / 64))) }
-                } else { DMA_LAUNCH(128, 128, 2, 2, 3, dim3(t128)) }
-            } else if (N > 32) {
-                // fewer 128-row tiles than two per CU: 64-row tiles (three workgroups per CU fit) run the map in one round instead of
-                // a round and a tail (conv3x3 64 -> 64 @ 8x60x80: 300 workgroups of 128 x 64 = 1.17 rounds)
-                if (bk64 && gm < 512 && d->KH * d->KW > 1) { DMA_LAUNCH_64(64, 64, 2, 2, 3, dim3((M + 63) / 64)) }      // same box: 18 -> 12 us, step -0.1 ms; 1x1: no gain
-                else DMA_LAUNCH(128, 64, 2, 2, 4, dim3(gm))
-            } else {
-                DMA_LAUNCH(128, 32, 4, 1, 4, dim3(gm))
-            }
-#undef DMA_LAUNCH
-#undef DMA_LAUNCH_64
-#undef DMA_LAUNCH_G64
-#undef DMA_LAUNCH_K
-#undef DMA_LAUNCH_G
-            GWD_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-    if (d->gate && d->gate_act == GWD_ACT_GELU) return -4;       // GELU gate: LDS-DMA tile kernels only; the caller applies it in a pass of its own
-    // fewer than two tiles per CU (the 60/120-channel pyramid at 1/8 resolution: 300 tiles of 128 rows = one full round plus
-    // a tail round of 44): quarter tiles give four times as many workgroups
-    const bool quarter = N > 32 && gm * ((N + 127) / 128) < 512;
-    if (N % 160 == 0) {                       // 160 / 320 channel pyramids: exact tiles, no padded columns
-        igemm_fwd_kernel<T, 128, 160, 4, 1, BK><<<dim3(gm, N / 160), 256, 0, s>>>(*d);
-    } else if (quarter) {
-        igemm_fwd_kernel<T, 64, 64, 2, 2, BK><<<dim3((M + 63) / 64, (N + 63) / 64), 256, 0, s>>>(*d);
-    } else if (N > 64) {
-        igemm_fwd_kernel<T, 128, 128, 2, 2, BK><<<dim3(gm, (N + 127) / 128), 256, 0, s>>>(*d);
-    } else if (N > 32) {
-        igemm_fwd_kernel<T, 128, 64, 2, 2, BK><<<dim3(gm, 1), 256, 0, s>>>(*d);
-    } else {
-        igemm_fwd_kernel<T, 128, 32, 4, 1, BK><<<dim3(gm, 1), 256, 0, s>>>(*d);
-    }
+    const ConvPlan p = plan_forward(*d, dma_enabled());
+    if (p.family == ConvFamily::DECLINED) return p.rc;
+    const int rc = p.family == ConvFamily::KSPLIT ? launch_ksplit(p, d, s) : p.family == ConvFamily::DMA ? launch_dma(p, d, s)
+                 : d->dtype == GWD_BF16 ? launch_staged<__bf16>(p, d, s) : launch_staged<float>(p, d, s);
+    if (rc) return rc;
     GWD_CHECK_LAUNCH();
     return 0;
 }
 
+// ---- weight gradient
+// Tile shapes measured and dropped: 160 x 256 / 128 x 256 (one workgroup per CU: -1 ms per step in all), the 3-stage ring for
+// 160 x 128 (+3-4 %), 64 x 64 for the narrow layers.  Each tile exists for FAST = 0 general | 1 same-size stride 1 | 2 plain GEMM;
+// the first N_WGRAD_GROUPED also as igemm_wgrad_group_kernel.
+struct WgradTile { int BN, BK, WN, WK, STAGES; };
+constexpr WgradTile WGRAD_TILES[] = {{128, 128, 2, 2, 3}, {64, 64, 2, 2, 4}, {32, 128, 1, 4, 4},      // 32 x 128: narrow layers, no half-empty 64-row tile
+                                     {160, 128, 1, 4, 4}};                                              // 4 stages = 72 KB, still 2 per CU
+constexpr int N_WGRAD_TILES = 4, N_WGRAD_GROUPED = 3, WG_128x128 = 0, WG_64x64 = 1, WG_32x128 = 2, WG_160x128 = 3;
+enum class WgradFamily { TAPS, DMA, STAGED, DECLINED };
+struct WgradPlan {
+    WgradFamily family;
+    int tile, FAST;                                       // DMA: index into WGRAD_TILES.  STAGED: tile WG_128x128 or WG_64x64
+    int splits, m_per_block;                              // TAPS: m_per_block = chunks per split
+    unsigned grid[3], block, lds; int rc;                 // lds: dynamic LDS bytes.  DECLINED: rc = what the entry point returns
+};
+
 #ifndef GWD_WG_BAL1
 #define GWD_WG_BAL1 1.3e12     // nominal flush rate (bytes/s) behind the split count of grouped 3x3 / strided weight gradients (0 = fill the chip with each layer: +0.15 ms per step)
 #endif
-constexpr int wgrad_target_blocks(int resident) { return resident; }     // exactly one full round of resident workgroups (no tail round)
-constexpr int wgrad_per_cu_128() { return 2; }                            // resident 128 x 128 weight-gradient workgroups per CU the split count aims at
-
-static void wgrad_split(int M, int tiles, int rm, int &splits, int &m_per_block, int resident = 768, double balance = 0.0) {
-    // M-splits so that tiles x splits fills the chip's resident workgroup slots once; >= 8 reduction steps each
-    splits = wgrad_target_blocks(resident) / tiles;
-    if (splits * tiles < wgrad_target_blocks(resident) * 3 / 4) ++splits;     // far below a full round: round up instead
+constexpr int WGRAD_PER_CU_128 = 2;                       // resident 128 x 128 weight-gradient workgroups per CU the split count aims at (138 registers: 3 fit)
+void wgrad_split(int M, int tiles, int rm, int &splits, int &m_per_block, int resident = 768, double balance = 0.0) {
+    // M-splits so that tiles x splits fills the chip's resident workgroup slots exactly once (no tail round); >= 8 reduction steps each
+    splits = resident / tiles;
+    if (splits * tiles < resident * 3 / 4) ++splits;      // far below a full round: round up instead
     if (balance > 0.0) {
         // every split flushes tiles x (tile bytes) of fp32 atomics (~1.3 TB/s chip-wide) but shortens each workgroup's
         // serial chain of (M / 32 / splits) steps: time ~ steps * t_step / S + S * flush  ->  S* = sqrt(steps * t_step / flush),
@@ -2233,146 +2224,144 @@ static void wgrad_split(int M, int tiles, int rm, int &splits, int &m_per_block,
     splits = (M + m_per_block - 1) / m_per_block;
 }
 
-// gwd_conv_wgrad_batch: weight gradients on the two hot tile shapes (128 x 128, 64 x 64; every gather form) are collected here instead
-// of being launched one by one; a full group, and flush() at the end of the batch, runs as ONE igemm_wgrad_group_kernel launch: the
-// layers of a group fill the chip together, so each needs fewer, longer workgroups (fewer prologues and atomic flushes), and one
-// layer's flush runs beside another's reduction.
-struct WgradCollector {
-    static constexpr int NT_ = 3;
-    WgradGroup g[NT_][3];                                 // [128 x 128 | 64 x 64 | 32 x 128][gather form: 0 general, 1 same-size stride 1, 2 plain GEMM]
-    int total[NT_][3];
-    hipStream_t s;
-    explicit WgradCollector(hipStream_t st) : s(st) {
-        for (int t = 0; t < NT_; ++t)
-            for (int f = 0; f < 3; ++f) g[t][f].n = total[t][f] = 0;
-    }
-    void launch(int t, int f) {
-        WgradGroup &gr = g[t][f];
-        if (!gr.n) return;
-        const int tot = total[t][f];
-        if (t == 0) {
-            if (f == 2) igemm_wgrad_group_kernel<128, 128, 2, 2, 3, 2><<<tot, 256, 0, s>>>(gr);
-            else if (f == 1) igemm_wgrad_group_kernel<128, 128, 2, 2, 3, 1><<<tot, 256, 0, s>>>(gr);
-            else igemm_wgrad_group_kernel<128, 128, 2, 2, 3, 0><<<tot, 256, 0, s>>>(gr);
-        } else if (t == 1) {
-            if (f == 2) igemm_wgrad_group_kernel<64, 64, 2, 2, 4, 2><<<tot, 256, 0, s>>>(gr);
-            else if (f == 1) igemm_wgrad_group_kernel<64, 64, 2, 2, 4, 1><<<tot, 256, 0, s>>>(gr);
-            else igemm_wgrad_group_kernel<64, 64, 2, 2, 4, 0><<<tot, 256, 0, s>>>(gr);
-        } else {
-            if (f == 2) igemm_wgrad_group_kernel<32, 128, 1, 4, 4, 2><<<tot, 256, 0, s>>>(gr);
-            else if (f == 1) igemm_wgrad_group_kernel<32, 128, 1, 4, 4, 1><<<tot, 256, 0, s>>>(gr);
-            else igemm_wgrad_group_kernel<32, 128, 1, 4, 4, 0><<<tot, 256, 0, s>>>(gr);
-        }
-        gr.n = total[t][f] = 0;
-    }
-    bool take(int bn, int bk, int fast, const gwd_conv_desc &d, float *dw, int m_per_block, int blocks) {
-        if (fast < 0 || fast > 2 || !((bn == 128 && bk == 128) || (bn == 64 && bk == 64) || (bn == 32 && bk == 128))) return false;
-        const int t = bn == 128 ? 0 : (bn == 64 ? 1 : 2);
-        if (g[t][fast].n >= WG_GROUP) launch(t, fast);
-        WgradGroup &gr = g[t][fast];
-        const int i = gr.n++;
-        gr.d[i] = d;
-        gr.dw[i] = dw;
-        gr.m_per_block[i] = m_per_block;
-        gr.block0[i] = total[t][fast];
-        gr.blocks[i] = blocks;
-        total[t][fast] += (blocks + 7) & ~7;
-        return true;
-    }
-    void flush() {
-        for (int t = 0; t < NT_; ++t)
-            for (int f = 0; f < 3; ++f) launch(t, f);
-    }
-};
+// the split of an LDS-DMA weight gradient with `tiles` tiles of shape t; batched: the call came through gwd_conv_wgrad_batch
+void wgrad_dma_split(const WgradTile &t, int M, int tiles, int fast, bool batched, int &splits, int &m_per_block) {
+    const int lds = t.STAGES * 32 * (t.BN + t.BK) * 2;
+    int per_cu = (160 * 1024) / lds;                      // LDS-limited; the >= 128-wide tiles hold ~200 VGPRs
+    if (t.BN * t.BK > 128 * 128 && per_cu > 2) per_cu = 2;      // -> 2 waves per SIMD = 2 workgroups per CU
+    if (t.BN * t.BK == 128 * 128 && per_cu > WGRAD_PER_CU_128) per_cu = WGRAD_PER_CU_128;
+    // plain GEMMs: a step costs ~0.45 us, one split's flush tiles * BN * BK * 4 bytes at a NOMINAL 0.25 TB/s: the atomics themselves run
+    // at ~1.3 TB/s, but these layers run grouped (WgradCollector), the group fills the chip, and fewer, longer workgroups per layer
+    // pay fewer prologues and flushes - whole step, same box: rate 4e12 35.15 ms | 1.3e12 34.49 | 0.5e12 34.12 | 0.25e12 34.05 | 0.12e12 34.04;
+    // the same balance for the 3x3 layers outside a batch: +0.1 ... +0.4 ms, not applied
+    const double flush_bytes = (double)tiles * t.BN * t.BK * 4;
+    const double bal = fast == 2 ? 0.45e-6 * 0.25e12 / flush_bytes : (batched ? GWD_WG_BAL1 * 0.6e-6 / flush_bytes : 0.0);
+    wgrad_split(M, tiles, 32, splits, m_per_block, 256 * (per_cu > 4 ? 4 : per_cu), bal);
+}
 
-// 1 = launched wgrad_taps_kernel
-static int launch_wgrad_taps(const gwd_conv_desc *d, float *dw, hipStream_t s) {
-    if (d->dtype != GWD_BF16 || !d->zero_page) return 0;
-    if (d->gather != GWD_GATHER_CONV || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->Ho != d->Hi || d->Wo != d->Wi) return 0;
-    // measured against igemm_wgrad_dma_kernel<160,128>, same box (tools/convbench.py): 800 -> 320 at 8x120x160 1.17 -> 0.81 ms, 160 -> 160
-    // 0.133 -> 0.114 ms; 80 -> 160 0.081 -> 0.085 and 160 -> 160 on a pooled 8x60x80 map 0.057 -> 0.070 (the nine-tap flush of a
-    // workgroup - 184 KB of atomics - needs enough steps to pay for itself): those stay where they were
-    if ((d->Cout % 160) || (d->Cin % 8) || d->Cin < 160) return 0;
-    const long M = (long)d->B * d->Ho * d->Wo;
-    if (M < 131072) return 0;
+// cus: compute units of the device (wgrad_taps_kernel runs one round of them)
+WgradPlan plan_wgrad(const gwd_conv_desc &d, bool dma_on, bool batched, int cus) {
+    const int M = d.B * d.Ho * d.Wo, N = d.Cout, K = d.KH * d.KW * d.Cin;
+    const bool bf16 = d.dtype == GWD_BF16;
+    WgradPlan p{};
+    p.grid[1] = p.grid[2] = 1, p.block = 256;
+    if (bf16 && dma_on && d.zero_page && (d.Cin % 8) == 0 && (N % 8) == 0) {
+        // 3x3 / stride 1 / pad 1 onto 160-wide outputs of big maps: wgrad_taps_kernel.  Measured against igemm_wgrad_dma_kernel<160,128>,
+        // same box (tools/convbench.py): 800 -> 320 at 8x120x160 1.17 -> 0.81 ms, 160 -> 160 0.133 -> 0.114 ms; 80 -> 160 0.081 -> 0.085
+        // and 160 -> 160 on a pooled 8x60x80 map 0.057 -> 0.070 (the nine-tap flush of a workgroup - 184 KB of atomics - needs enough
+        // steps to pay for itself): those stay where they were
+        if (d.gather == GWD_GATHER_CONV && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Ho == d.Hi && d.Wo == d.Wi && (N % 160) == 0 &&
+            d.Cin >= 160 && M >= 131072) {
+            const int tiles = ((d.Cin + 31) / 32) * (N / 160), total = d.B * d.Ho * ((d.Wo + 31) / 32);
+            const int splits = cus / tiles < 1 ? 1 : cus / tiles;
+            const int cps = (total + splits - 1) / splits < 8 ? 8 : (total + splits - 1) / splits;
+            p.family = WgradFamily::TAPS;
+            p.splits = (total + cps - 1) / cps, p.m_per_block = cps;
+            p.grid[0] = tiles * p.splits, p.block = 64 * WT_W, p.lds = WT_STAGES * WT_STAGE;
+            return p;
+        }
+        p.family = WgradFamily::DMA;
+        if (d.gather == GWD_GATHER_CONV && d.stride == 1) {
+            if (d.KH == 1 && d.KW == 1 && d.pad == 0) p.FAST = 2;
+            else if (d.Ho == d.Hi && d.Wo == d.Wi && d.Wo >= 11) p.FAST = 1;
+        }
+        p.tile = (N % 160 == 0 && K >= 128) ? WG_160x128 : ((N > 64 && K > 64) ? WG_128x128 : ((N <= 32 && K >= 128) ? WG_32x128 : WG_64x64));
+        const WgradTile &t = WGRAD_TILES[p.tile];
+        const int tiles = ((N + t.BN - 1) / t.BN) * ((K + t.BK - 1) / t.BK);
+        wgrad_dma_split(t, M, tiles, p.FAST, batched, p.splits, p.m_per_block);
+        p.grid[0] = (unsigned)tiles * p.splits;
+        return p;
+    }
+    p.family = WgradFamily::STAGED;
+    p.tile = (N > 64 && K > 64) ? WG_128x128 : WG_64x64;
+    const int bn = WGRAD_TILES[p.tile].BN, bk = WGRAD_TILES[p.tile].BK;
+    wgrad_split(M, ((N + bn - 1) / bn) * ((K + bk - 1) / bk), bf16 ? Cfg<__bf16>::BK : Cfg<float>::BK, p.splits, p.m_per_block);
+    p.grid[0] = (K + bk - 1) / bk, p.grid[1] = (N + bn - 1) / bn, p.grid[2] = p.splits;
+    if (p.grid[1] > 65535 || p.grid[2] > 65535) p.family = WgradFamily::DECLINED, p.rc = -8;
+    return p;
+}
+
+int cu_count() {
     static int cus = 0;
     if (!cus) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     }
-    static bool attr = false;
-    constexpr int LDS = WT_STAGES * WT_STAGE;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void *)wgrad_taps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr = true;
-    }
-    const int tiles = ((d->Cin + 31) / 32) * (d->Cout / 160);
-    const int total = d->B * d->Ho * ((d->Wo + 31) / 32);
-    int splits = cus / tiles;
-    if (splits < 1) splits = 1;
-    int cps = (total + splits - 1) / splits;
-    if (cps < 8) cps = 8;
-    splits = (total + cps - 1) / cps;
-    const int wgs = tiles * splits;
-    wgrad_taps_kernel<<<wgs, 64 * WT_W, LDS, s>>>(*d, dw, cps, wgs);
-    return 1;
+    return cus;
 }
 
-template <typename T>
-int launch_wgrad(const gwd_conv_desc *d, float *dw, hipStream_t s, WgradCollector *coll = nullptr) {
-    constexpr int RM = Cfg<T>::BK;
-    const int M = d->B * d->Ho * d->Wo, N = d->Cout, K = d->KH * d->KW * d->Cin;
-    int splits, m_per_block;
-    if constexpr (sizeof(T) == 2) {
-        if (dma_enabled() && d->zero_page && (d->Cin % 8) == 0 && (N % 8) == 0) {
-#define WG_LAUNCH(BN_, BK_, WN_, WK_, ST_)                                                                   \
-    {                                                                                                        \
-        const int tiles = ((N + BN_ - 1) / BN_) * ((K + BK_ - 1) / BK_);                                     \
-        const int lds = ST_ * 32 * (BN_ + BK_) * 2;                                                          \
-        int per_cu = (160 * 1024) / lds;                  /* LDS-limited; the >= 128-wide tiles hold ~200 VGPRs */      \
-        if (BN_ * BK_ > 128 * 128 && per_cu > 2) per_cu = 2;   /* -> 2 waves per SIMD = 2 workgroups per CU */          \
-        if (BN_ * BK_ == 128 * 128 && per_cu > wgrad_per_cu_128()) per_cu = wgrad_per_cu_128();  /* 138 registers: 3 fit */      \
-        /* plain GEMMs: a step costs ~0.45 us, one split's flush tiles * BN * BK * 4 bytes at a NOMINAL 0.25 TB/s: the atomics themselves run */  \
-        /* at ~1.3 TB/s, but these layers run grouped (WgradCollector), the group fills the chip, and fewer, longer workgroups per layer */   \
-        /* pay fewer prologues and flushes - whole step, same box: rate 4e12 35.15 ms | 1.3e12 34.49 | 0.5e12 34.12 | 0.25e12 34.05 | 0.12e12 34.04; */ \
-        /* the same balance for the 3x3 layers (not grouped): +0.1 ... +0.4 ms, not applied */ \
-        const double bal = fast == 2 ? 0.45e-6 * 0.25e12 / ((double)tiles * BN_ * BK_ * 4) : (coll ? GWD_WG_BAL1 * 0.6e-6 / ((double)tiles * BN_ * BK_ * 4) : 0.0);                         \
-        wgrad_split(M, tiles, 32, splits, m_per_block, 256 * (per_cu > 4 ? 4 : per_cu), bal);                \
-        dim3 grid((unsigned)tiles * splits);                                                                 \
-        if (coll && coll->take(BN_, BK_, fast, *d, dw, m_per_block, tiles * splits)) { /* runs at flush() */ }             \
-        else if (fast == 2) igemm_wgrad_dma_kernel<BN_, BK_, WN_, WK_, ST_, 2><<<grid, 256, 0, s>>>(*d, dw, m_per_block);      \
-        else if (fast == 1) igemm_wgrad_dma_kernel<BN_, BK_, WN_, WK_, ST_, 1><<<grid, 256, 0, s>>>(*d, dw, m_per_block); \
-        else igemm_wgrad_dma_kernel<BN_, BK_, WN_, WK_, ST_, 0><<<grid, 256, 0, s>>>(*d, dw, m_per_block);   \
+// gwd_conv_wgrad_batch: weight gradients on the grouped tile shapes (every gather form) are collected here instead of being launched
+// one by one; a full group, and flush() at the end of the batch, runs as ONE igemm_wgrad_group_kernel launch: the layers of a group
+// fill the chip together, so each needs fewer, longer workgroups (fewer prologues and atomic flushes), and one layer's flush runs
+// beside another's reduction.
+struct WgradCollector {
+    WgradGroup g[N_WGRAD_GROUPED][3];                     // [tile][FAST]
+    int total[N_WGRAD_GROUPED][3];
+    hipStream_t s;
+    explicit WgradCollector(hipStream_t st) : s(st) {
+        for (int t = 0; t < N_WGRAD_GROUPED; ++t)
+            for (int f = 0; f < 3; ++f) g[t][f].n = total[t][f] = 0;
     }
-            if (launch_wgrad_taps(d, dw, s)) {
-                GWD_CHECK_LAUNCH();
-                return 0;
-            }
-            int fast = 0;
-            if (d->gather == GWD_GATHER_CONV && d->stride == 1) {
-                if (d->KH == 1 && d->KW == 1 && d->pad == 0) fast = 2;
-                else if (d->Ho == d->Hi && d->Wo == d->Wi && d->Wo >= 11) fast = 1;
-            }
-            // tile shapes measured and dropped: 160 x 256 / 128 x 256 (one workgroup per CU: -1 ms per step in all), the 3-stage ring for
-            // 160 x 128 (+3-4 %), 64 x 64 for the narrow layers
-            if (N % 160 == 0 && K >= 128) WG_LAUNCH(160, 128, 1, 4, 4)      // 4 stages = 72 KB, still 2 per CU
-            else if (N > 64 && K > 64) WG_LAUNCH(128, 128, 2, 2, 3)
-            else if (N <= 32 && K >= 128) WG_LAUNCH(32, 128, 1, 4, 4)      // narrow layers: no half-empty 64-row tile
-            else WG_LAUNCH(64, 64, 2, 2, 4)
-#undef WG_LAUNCH
-            GWD_CHECK_LAUNCH();
+    void launch(int t, int f) {
+        WgradGroup &gr = g[t][f];
+        if (!gr.n) return;
+        (void)with_index<N_WGRAD_GROUPED * 3>([&](int i) { return i == t * 3 + f; }, [&](auto I) {
+            constexpr WgradTile w = WGRAD_TILES[decltype(I)::value / 3];
+            igemm_wgrad_group_kernel<w.BN, w.BK, w.WN, w.WK, w.STAGES, decltype(I)::value % 3><<<total[t][f], 256, 0, s>>>(gr);
             return 0;
-        }
+        });
+        gr.n = total[t][f] = 0;
     }
-    const bool big = (N > 64 && K > 64);
-    const int bn = big ? 128 : 64, bk = big ? 128 : 64;
-    wgrad_split(M, ((N + bn - 1) / bn) * ((K + bk - 1) / bk), RM, splits, m_per_block);
-    dim3 grid((K + bk - 1) / bk, (N + bn - 1) / bn, splits);
-    if (grid.y > 65535 || grid.z > 65535) return -8;
-    if (big)
-        igemm_wgrad_kernel<T, 128, 128><<<grid, 256, 0, s>>>(*d, dw, m_per_block);
-    else
-        igemm_wgrad_kernel<T, 64, 64><<<grid, 256, 0, s>>>(*d, dw, m_per_block);
+    bool take(const WgradPlan &p, const gwd_conv_desc &d, float *dw) {
+        if (p.family != WgradFamily::DMA || p.tile >= N_WGRAD_GROUPED) return false;
+        if (g[p.tile][p.FAST].n >= WG_GROUP) launch(p.tile, p.FAST);
+        WgradGroup &gr = g[p.tile][p.FAST];
+        const int i = gr.n++;
+        gr.d[i] = d;
+        gr.dw[i] = dw;
+        gr.m_per_block[i] = p.m_per_block;
+        gr.block0[i] = total[p.tile][p.FAST];
+        gr.blocks[i] = (int)p.grid[0];
+        total[p.tile][p.FAST] += ((int)p.grid[0] + 7) & ~7;
+        return true;
+    }
+    void flush() {
+        for (int t = 0; t < N_WGRAD_GROUPED; ++t)
+            for (int f = 0; f < 3; ++f) launch(t, f);
+    }
+};
+
+template <typename T>
+void launch_wgrad_staged(const WgradPlan &p, const gwd_conv_desc *d, float *dw, hipStream_t s) {
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    if (p.tile == WG_128x128) igemm_wgrad_kernel<T, 128, 128><<<grid, p.block, 0, s>>>(*d, dw, p.m_per_block);
+    else igemm_wgrad_kernel<T, 64, 64><<<grid, p.block, 0, s>>>(*d, dw, p.m_per_block);
+}
+int launch_wgrad(const gwd_conv_desc *d, float *dw, hipStream_t s, WgradCollector *coll = nullptr) {
+    const WgradPlan p = plan_wgrad(*d, dma_enabled(), coll != nullptr, cu_count());
+    int rc = p.rc;
+    switch (p.family) {
+        case WgradFamily::DECLINED: return rc;
+        case WgradFamily::TAPS: {
+            static bool attr = false;
+            if (!attr) {
+                (void)hipFuncSetAttribute((const void *)wgrad_taps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+                attr = true;
+            }
+            wgrad_taps_kernel<<<p.grid[0], p.block, p.lds, s>>>(*d, dw, p.m_per_block, (int)p.grid[0]);
+            break;
+        }
+        case WgradFamily::DMA:
+            if (coll && coll->take(p, *d, dw)) break;      // runs at flush()
+            rc = with_index<N_WGRAD_TILES * 3>([&](int i) { return i == p.tile * 3 + p.FAST; }, [&](auto I) {
+                constexpr WgradTile w = WGRAD_TILES[decltype(I)::value / 3];
+                igemm_wgrad_dma_kernel<w.BN, w.BK, w.WN, w.WK, w.STAGES, decltype(I)::value % 3><<<p.grid[0], p.block, 0, s>>>(*d, dw, p.m_per_block);
+                return 0;
+            });
+            break;
+        case WgradFamily::STAGED: d->dtype == GWD_BF16 ? launch_wgrad_staged<__bf16>(p, d, dw, s) : launch_wgrad_staged<float>(p, d, dw, s); break;
+    }
+    if (rc) return rc;
     GWD_CHECK_LAUNCH();
     return 0;
 }
@@ -2407,7 +2396,7 @@ extern "C" int gwd_conv_forward(const gwd_conv_desc *d, void *stream) {
         GWD_CHECK_LAUNCH();
         return 0;
     }
-    rc = d->dtype == GWD_BF16 ? launch_fwd<__bf16>(d, (hipStream_t)stream) : launch_fwd<float>(d, (hipStream_t)stream);
+    rc = launch_fwd(d, (hipStream_t)stream);
     if (rc == 0 && trace_conv()) trace_line("fwd", d);     // one line per LAUNCH (a refused ConvLn request, -4, launched nothing): tools/conv_instep.py
     return rc;
 }
@@ -2421,8 +2410,7 @@ extern "C" int gwd_conv_wgrad(const gwd_conv_desc *d, float *dw, void *stream) {
         GWD_CHECK_LAUNCH();
         return 0;
     }
-    return d->dtype == GWD_BF16 ? launch_wgrad<__bf16>(d, dw, (hipStream_t)stream)
-                                : launch_wgrad<float>(d, dw, (hipStream_t)stream);
+    return launch_wgrad(d, dw, (hipStream_t)stream);
 }
 
 extern "C" int gwd_conv_wgrad_batch(const gwd_conv_desc *descs, float *const *dws, int32_t n, void *stream) {
@@ -2438,7 +2426,7 @@ extern "C" int gwd_conv_wgrad_batch(const gwd_conv_desc *descs, float *const *dw
         const gwd_conv_desc *d = descs + i;
         if (trace_conv()) trace_line("wgrad", d);
         if (gwd_thin_conv_wgrad(d, dws[i], s) || gwd_tile_conv_wgrad(d, dws[i], s)) continue;
-        const int rc = d->dtype == GWD_BF16 ? launch_wgrad<__bf16>(d, dws[i], s, &coll) : launch_wgrad<float>(d, dws[i], s);
+        const int rc = launch_wgrad(d, dws[i], s, &coll);
         if (rc) return rc;
     }
     coll.flush();
