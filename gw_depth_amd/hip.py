@@ -33,7 +33,7 @@ ENTRY_POINTS = [
     "gwd_anchor_depth_forward", "gwd_anchor_depth_backward", "gwd_mha_flash_forward", "gwd_mha_flash_backward",
     "gwd_ref_scores_forward", "gwd_ref_scores_backward", "gwd_ref_mix_forward", "gwd_ref_mix_backward", "gwd_unpad_add_batch", "gwd_stem_pack", "gwd_stem_forward", "gwd_pos_sine", "gwd_silog_finalize", "gwd_psp_pool_forward", "gwd_psp_pool_backward",
     "gwd_match_cost", "gwd_set_losses_forward", "gwd_set_losses_backward", "gwd_resample_u8_pass", "gwd_gather2d", "gwd_point_sample_backward_gather", "gwd_point_sample_framed_forward", "gwd_point_sample_framed_backward", "gwd_stride_place", "gwd_color_adjust", "gwd_bmm",
-    "gwd_dense_postprocess", "gwd_line_postprocess",
+    "gwd_dense_postprocess", "gwd_line_postprocess", "gwd_line_score",
 ]
 
 
@@ -223,6 +223,8 @@ class HipLibrary:
         L.gwd_eval_accumulate.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, i64, f32, f32, i32, i32, vp]
         L.gwd_dense_postprocess.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp]
         L.gwd_line_postprocess.argtypes = [vp] * 7 + [i32, i32, i32, f32, vp]
+        dp = ctypes.POINTER(ctypes.c_double)
+        L.gwd_line_score.argtypes = [vp] * 5 + [dp, i32, dp, i32] + [vp] * 4 + [i32] * 4 + [i64, i64, vp]
         L.gwd_softmax_masked_forward.argtypes = [vp, vp, vp, i64, i32, i64, ctypes.c_float, i32, vp]
         L.gwd_softmax_scaled_backward.argtypes = [vp, vp, vp, i64, i32, ctypes.c_float, i32, vp]
         L.gwd_resample_backward_sep.argtypes = [vp, vp, vp] + [i32] * 9 + [vp]
@@ -469,6 +471,27 @@ class HipLibrary:
         self._check(self.lib.gwd_line_postprocess(
             _ptr(logits), _ptr(lines), _ptr(sizes), _ptr(scores), _ptr(lines_px), _ptr(order), _ptr(count), B, Q, ld, float(thresh),
             self._stream(logits, lines, sizes, scores, lines_px, order, count)), "gwd_line_postprocess")
+
+    def line_score(self, logits, lines, sizes, gt, gt_count, nms_thresholds, sap_thresholds, flag, kept_lines, score, gt_seen, slot):
+        """gwd_line_score: logits (B,Q,2) / lines (B,Q,ld) / gt (B,G,4) fp32, sizes (B,2) / gt_count (B,) int32; the outputs are the
+        accumulator's whole buffers flag (T,S,cap,Q) uint8, kept_lines (T,cap,Q,4) f64, score (cap,Q) fp32, gt_seen (cap,) int32, of
+        which images slot .. slot + B - 1 are written.  Q, G <= 1024; at most four thresholds of either kind."""
+        for t, dt in ((logits, torch.float32), (lines, torch.float32), (sizes, torch.int32), (gt, torch.float32), (gt_count, torch.int32),
+                      (flag, torch.uint8), (kept_lines, torch.float64), (score, torch.float32), (gt_seen, torch.int32)):
+            if t.dtype != dt:
+                raise TypeError("gwd_line_score: expected %s, got %s" % (dt, t.dtype))
+        B, Q, ld = lines.shape
+        G, T, S, cap = gt.shape[1], len(nms_thresholds), len(sap_thresholds), score.shape[0]
+        if tuple(logits.shape) != (B, Q, 2) or tuple(sizes.shape) != (B, 2) or tuple(gt.shape) != (B, G, 4) or gt_count.numel() != B \
+                or tuple(flag.shape) != (T, S, cap, Q) or tuple(kept_lines.shape) != (T, cap, Q, 4) or tuple(score.shape) != (cap, Q) \
+                or gt_seen.numel() != cap or slot < 0 or slot + B > cap:
+            raise ValueError("gwd_line_score: operand sizes do not match (B, Q, G, T, S, capacity, slot) = %r" % ((B, Q, G, T, S, cap, slot),))
+        nms = (ctypes.c_double * T)(*[float(v) for v in nms_thresholds])
+        sap = (ctypes.c_double * S)(*[float(v) for v in sap_thresholds])
+        self._check(self.lib.gwd_line_score(
+            _ptr(logits), _ptr(lines), _ptr(sizes), _ptr(gt), _ptr(gt_count), nms, T, sap, S, _ptr(flag), _ptr(kept_lines), _ptr(score),
+            _ptr(gt_seen), B, Q, ld, G, cap, int(slot),
+            self._stream(logits, lines, sizes, gt, gt_count, flag, kept_lines, score, gt_seen)), "gwd_line_score")
 
     def plane_loss_forward(self, depth, valid, tri, n_planes, P, H, W, min_area, workspace, stats, loss):
         self._check(self.lib.gwd_plane_loss_forward(_ptr(depth), _ptr(valid), _ptr(tri), _ptr(n_planes), P, H, W, min_area,

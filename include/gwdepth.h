@@ -517,6 +517,31 @@ int gwd_dense_postprocess(const void *depth, const void *seg_logits, int64_t seg
 int gwd_line_postprocess(const float *logits, const float *lines, const int32_t *sizes, float *scores, float *lines_px,
                          int32_t *order, int32_t *count, int32_t B, int32_t Q, int32_t ld, float thresh, void *stream);
 
+/* Structural-AP scoring of the detected lines, one workgroup per image (csrc/linescore.hip; the scalar geometry is csrc/linescore.h).
+ * Replaces, per image, what the reference does on the host between evaluate(save_line=True) and its offline scripts:
+ *   score = softmax probability of class 0 (src/engine_glassrgbd.py:287,297); the first two points of every query as (y, x) times
+ *   (h, w) in fp32; the duplicate trim at the first i > 0 whose line (all ld values) equals line 0 (evaluation/eval_post_online.py:
+ *   127-131); L-CNN's line NMS postprocess(lines, scores, diag * t, tol = 0, do_clip = False) (eval_post_online.py:44-91,142) for
+ *   each of the T thresholds, with the lines in QUERY order as the reference passes them (not score order); the kept lines times
+ *   (128 / h, 128 / w) (:174-175); the second duplicate trim (evaluation/eval-sAP-glassrgbd.py:55-59); and msTPFP
+ *   (evaluation/lcnn/metric.py:194-210) against gt * 128 for each of the S squared-distance thresholds.
+ * Precision: pinned to f64 after the fp32 scaling, no contraction - the reference's own precision depends on its NumPy version.
+ *   logits [B][Q][2] fp32, lines [B][Q][ld] fp32 (ld 4 or 6, x before y), sizes [B][2] int32 (h, w), gt [B][G][4] fp32 normalised
+ *   (x1, y1, x2, y2) of which the first gt_count[b] (int32, clamped to [0, G]) rows count (gt may be NULL when G = 0; an image
+ *   without ground truth scores every kept line as a false positive); nms_thresholds [T] and sap_thresholds [S]: HOST arrays,
+ *   1 <= T, S <= 4, fractions of the image diagonal and squared distances in the 128 x 128 space.
+ * Outputs are an accumulator's buffers of `capacity` image slots; images slot .. slot + B - 1 are written, every element of them:
+ *   flag [T][S][capacity][Q] uint8: 0 false positive, 1 true positive, 2 not scored (suppressed or behind a trim);
+ *   kept_lines [T][capacity][Q][4] f64: (y1, x1, y2, x2) of the kept (clipped) lines in the 128 x 128 space, zeros elsewhere;
+ *   score [capacity][Q] fp32; gt_seen [capacity] int32 = the clamped gt_count.
+ * A kept line is a true positive iff its distance is below the threshold and no EARLIER kept line with the same choice of ground
+ * truth was (first minimum on ties) - the hit array of msTPFP without its serial walk.
+ * -1 on bad arguments (slot + B > capacity among them), -2 when Q > 1024 or G > 1024.  One launch, no atomics, no memset. */
+int gwd_line_score(const float *logits, const float *lines, const int32_t *sizes, const float *gt, const int32_t *gt_count,
+                   const double *nms_thresholds, int32_t T, const double *sap_thresholds, int32_t S, uint8_t *flag,
+                   double *kept_lines, float *score, int32_t *gt_seen, int32_t B, int32_t Q, int32_t ld, int32_t G,
+                   int64_t capacity, int64_t slot, void *stream);
+
 /* PlaneLoss (src/models/glassrgbd.py:385-450, --with_plane_norm_loss) of ONE image, on the device: Sobel normals of the
  * predicted depth (src/models/losses/sobel.py:5-27), the masks of up to P <= 64 line triangles restricted to the valid
  * pixels (the reference: matplotlib.path.Path.contains_points on the host; same crossing test here, exact in integers),
