@@ -268,12 +268,13 @@ class HipLibrary:
     # ------------------------------------------------------------------ entry points
     @staticmethod
     def _desc(x, w, y, dims, z=None, scale=None, shift=None, residual=None, stride=1, pad=0,
-              gather=GATHER_CONV, virt=(0, 0), act=ACT_NONE, act_scale=1.0, mult=None, gate=None, gate_act=ACT_NONE, ln=None):
+              gather=GATHER_CONV, virt=(0, 0), act=ACT_NONE, act_scale=1.0, mult=None, gate=None, gate_act=ACT_NONE, ln=None,
+              zero_page=True):
         B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW = dims
         d = ConvDesc()
         d.x, d.w, d.y, d.z = _ptr(x), _ptr(w), _ptr(y), _ptr(z)
         d.scale, d.shift, d.residual = _ptr(scale), _ptr(shift), _ptr(residual)
-        d.zero_page = _zero_page(x.device)
+        d.zero_page = _zero_page(x.device) if zero_page else None      # False: the register-staged kernels (gwd_conv_desc.zero_page = NULL)
         d.mult = _ptr(mult)
         d.gate, d.gate_act = _ptr(gate), (gate_act if gate is not None else ACT_NONE)
         d.B, d.Hi, d.Wi, d.Cin, d.Ho, d.Wo, d.Cout, d.KH, d.KW = B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW
@@ -287,7 +288,8 @@ class HipLibrary:
         """dims = (B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW); kw: z scale shift residual stride pad gather virt act act_scale mult
         gate gate_act (the epilogue's last step: backward of the activation whose output is `gate`); ln=(mean, rstd, C): the ConvLn
         epilogue (LayerNorm over the first C channels, scale / shift = gamma / beta) - returns False when the library has no fused
-        kernel for the shape (nothing was launched)."""
+        kernel for the shape (nothing was launched).  zero_page=False leaves gwd_conv_desc.zero_page NULL: the register-staged
+        kernels instead of the LDS-DMA route (the default, True, hands over the device's zero page)."""
         d = self._desc(x, w, y, dims, **kw)
         rc = self.lib.gwd_conv_forward(ctypes.byref(d), self._stream(x, w, y))
         if rc == -4 and kw.get("ln") is not None:

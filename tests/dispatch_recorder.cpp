@@ -4,6 +4,11 @@
 // gwd_conv_wgrad and gwd_conv_wgrad_batch (and the three weight-copy entry points) and prints one line per call:
 //   <call> <descriptor> rc=<return code> { | <mangled kernel> <grid> <block> <dynamic LDS> <int arguments> }
 // The output depends on the host logic of the three objects and on the stubbed CU count (256) only.
+// With the argument `--stdin` it walks no grid: it reads one call per line from standard input, as plain numbers,
+//   F <B Hi Wi Cin Cout k s gather dtype zero_page> <kind 0..11> <ln_C, 0 = Cout> <act_scale: 0 = 1.0 | 1 = 0.7>
+//   W <B Hi Wi Cin Cout k s gather dtype zero_page> <scaled 0|1>
+//   B <n> <B Hi Wi Cin Cout k s gather dtype zero_page> <scaled 0|1>      n jobs of one layer in one gwd_conv_wgrad_batch call, job i on B + i images
+// and prints the same records (tools/make_conv_witnesses.py and tests/test_conv_witnesses.py drive it).
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -246,11 +251,71 @@ void record_weight_copies() {
     g_line = "U jobs=2";
     end_record(gwd_unpad_add_batch(jobs, 2, nullptr));
 }
+
+// one call per input line, see the head of the file; a malformed line ends the run with status 2
+int replay_stdin() {
+    char line[256];
+    while (fgets(line, sizeof line, stdin)) {
+        char call = 0;
+        int n = 1, v[10], a = 0, b = 0, as = 0, used = 0;
+        if (line[0] == '#' || line[0] == '\n') continue;
+        if (sscanf(line, " %c%n", &call, &used) != 1) return 2;
+        const char *p = line + used;
+        if (call == 'B') {
+            if (sscanf(p, "%d%n", &n, &used) != 1 || n < 1 || n > 64) return 2;
+            p += used;
+        }
+        for (int i = 0; i < 10; ++i) {
+            if (sscanf(p, "%d%n", &v[i], &used) != 1) return 2;
+            p += used;
+        }
+        if (call == 'F' && sscanf(p, "%d %d %d", &a, &b, &as) != 3) return 2;
+        if ((call == 'W' || call == 'B') && sscanf(p, "%d", &a) != 1) return 2;
+        gwd_conv_desc d = make_desc(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9] != 0);
+        char buf[48];
+        if (call == 'F') {
+            if (a < 0 || a >= N_KINDS) return 2;
+            set_epilogue(d, a);
+            if (d.ln_mean && b > 0) d.ln_C = b;
+            if (as) d.act_scale = 0.7f;
+            g_line = "F";
+            put_desc(d);
+            snprintf(buf, sizeof buf, " %s zp=%d lnC=%d as=%d", KINDS[a], v[9] != 0, d.ln_C, as != 0);
+            g_line += buf;
+            end_record(gwd_conv_forward(&d, nullptr));
+        } else if (call == 'W') {
+            if (a) d.scale = (float *)fake(4);
+            g_line = "W";
+            put_desc(d);
+            snprintf(buf, sizeof buf, " scaled=%d zp=%d", a != 0, v[9] != 0);
+            g_line += buf;
+            end_record(gwd_conv_wgrad(&d, (float *)fake(12), nullptr));
+        } else if (call == 'B') {
+            std::vector<gwd_conv_desc> descs;
+            std::vector<float *> dws;
+            snprintf(buf, sizeof buf, "B n=%d", n);
+            g_line = buf;
+            for (int i = 0; i < n; ++i) {
+                descs.push_back(make_desc(v[0] + i, v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9] != 0));
+                if (a) descs.back().scale = (float *)fake(4);
+                dws.push_back((float *)fake(12 + i));
+                put_desc(descs.back());
+            }
+            snprintf(buf, sizeof buf, " scaled=%d zp=%d", a != 0, v[9] != 0);
+            g_line += buf;
+            end_record(gwd_conv_wgrad_batch(descs.data(), dws.data(), n, nullptr));
+        } else {
+            return 2;
+        }
+    }
+    return 0;
+}
 }  // namespace
 
-int main() {
+int main(int argc, char **argv) {
     static char out_buf[1 << 20];
     setvbuf(stdout, out_buf, _IOFBF, sizeof out_buf);
+    if (argc > 1) return strcmp(argv[1], "--stdin") == 0 ? replay_stdin() : 2;
     record_forward();
     std::vector<gwd_conv_desc> pool;
     record_wgrad(pool);
