@@ -1348,8 +1348,16 @@ __device__ __forceinline__ void wgrad_dma_body(const gwd_conv_desc &d, float *__
         ++issued;
     };
 
+    // the bias gradient rides along (desc.dbias): the dY fragments of the waves wk == 0 cover every channel of the N tile once, and only
+    // the workgroups of the first K tile of their N tile add them up, over their own [m_begin, m_end).  Rows past m_end and columns past
+    // N come from the zero page.  Wave-uniform; the ring loop exists once per answer, so the dbias == NULL loop is the one it always was
+    const bool with_bias = d.dbias != nullptr && kb0 == 0 && __builtin_amdgcn_readfirstlane(wk) == 0;
+    float bsum[TN];
+#pragma unroll
+    for (int i = 0; i < TN; ++i) bsum[i] = 0.f;
+
     const int g = lane >> 4, t = lane & 15;
-    auto compute = [&](int stage) {
+    auto compute = [&](int stage, auto BIAS) {
         const char *Yb = smem + stage * STAGE_BYTES;
         const char *Xb = Yb + RM * YB;                            // == Yb + YI * 1024
 #pragma unroll
@@ -1366,6 +1374,17 @@ __device__ __forceinline__ void wgrad_dma_body(const gwd_conv_desc &d, float *__
                 u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)plo);
                 u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)phi);
                 af[i] = u.v;
+            }
+            if constexpr (decltype(BIAS)::value) {
+                // lane l holds channel (l & 31) of tile i at the 8 pixels 8 * (l >> 5) .. + 7 of this 16-pixel block: per-lane fp32 adds
+                // here, the two halves meet once after the loop
+#pragma unroll
+                for (int i = 0; i < TN; ++i) {
+                    float e = 0.f, o = 0.f;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) e += (float)af[i][2 * q], o += (float)af[i][2 * q + 1];
+                    bsum[i] += e + o;
+                }
             }
 #pragma unroll
             for (int j = 0; j < TK; ++j) {
@@ -1387,21 +1406,35 @@ __device__ __forceinline__ void wgrad_dma_body(const gwd_conv_desc &d, float *__
 #pragma unroll
     for (int s = 0; s < STAGES - 1; ++s)
         if (s < steps) issue(s);
-    for (int s = 0; s < steps; ++s) {
-        if (s + STAGES - 2 < steps) {
-            if (my_loads == IT)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IT * (STAGES - 2)) : "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((IT - 1) * (STAGES - 2)) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    auto ring = [&](auto BIAS) {
+        for (int s = 0; s < steps; ++s) {
+            if (s + STAGES - 2 < steps) {
+                if (my_loads == IT)
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IT * (STAGES - 2)) : "memory");
+                else
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((IT - 1) * (STAGES - 2)) : "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            __builtin_amdgcn_s_barrier();
+            if (s + STAGES - 1 < steps) issue((s + STAGES - 1) % STAGES);
+            compute(s % STAGES, BIAS);
         }
-        __builtin_amdgcn_s_barrier();
-        if (s + STAGES - 1 < steps) issue((s + STAGES - 1) % STAGES);
-        compute(s % STAGES);
-    }
+    };
+    if (with_bias) ring(std::true_type{});                  // every wave passes the same number of barriers on either side
+    else ring(std::false_type{});
 
     const int fr = lane & 31, fh = lane >> 5;
+    if (with_bias) {
+        // one atomic per channel per workgroup, in front of the weight flush and with no load in between (note below); the library
+        // refuses dbias together with scale, so the multiplier cannot reach these sums
+#pragma unroll
+        for (int i = 0; i < TN; ++i) {
+            const float sum = bsum[i] + __shfl_xor(bsum[i], 32);
+            const int n = n0 + wn * (BNW / WN) + i * 32 + fr;
+            if (fh == 0 && n < N) unsafeAtomicAdd(d.dbias + n, sum);
+        }
+    }
     // the per-row multiplier (folded FrozenBN) in a pass of its own, BEFORE the first atomic: a load between two atomics puts an
     // s_waitcnt vmcnt(0) - a wait for every atomic issued so far - in front of each multiply, and the flush runs at one atomic per
     // memory round trip (seen in the ISA in round 3; every BN-folded ResNet layer paid it)
@@ -1447,6 +1480,7 @@ struct WgradGroup {
     int m_per_block[WG_GROUP], block0[WG_GROUP], blocks[WG_GROUP];
     int n;
 };
+static_assert(sizeof(WgradGroup) <= 4096, "WgradGroup travels by value: the kernel-argument segment holds 4 KB");
 template <int BNW, int BKW, int WN, int WK, int STAGES, int FAST>
 __global__ __launch_bounds__(256) void igemm_wgrad_group_kernel(const WgradGroup g) {
     int ji = 0;
@@ -2382,9 +2416,11 @@ static void trace_line(const char *what, const gwd_conv_desc *d) {
 // thinconv.hip: streaming kernels for the 1-2 channel heads; return 1 when they took the problem
 int gwd_thin_conv_forward(const gwd_conv_desc *d, hipStream_t s);
 int gwd_thin_conv_wgrad(const gwd_conv_desc *d, float *dw, hipStream_t s);
+bool gwd_thin_conv_wgrad_accepts(const gwd_conv_desc *d);
 // tileconv.hip: halo-tiled 3x3 kernels for 32 / 64-channel layers on large maps; return 1 when they took the problem
 int gwd_tile_conv_forward(const gwd_conv_desc *d, hipStream_t s);
 int gwd_tile_conv_wgrad(const gwd_conv_desc *d, float *dw, hipStream_t s);
+bool gwd_tile_conv_wgrad_family(const gwd_conv_desc *d);
 
 extern "C" int gwd_conv_forward(const gwd_conv_desc *d, void *stream) {
     int rc = check_desc(d);
@@ -2401,10 +2437,21 @@ extern "C" int gwd_conv_forward(const gwd_conv_desc *d, void *stream) {
     return rc;
 }
 
+// Pure selection: which kernel family takes the weight gradient is decided by the thin / tile-conv acceptance tests and plan_wgrad,
+// none of which looks at the device (the CU count only sizes wgrad_taps_kernel's grid, so a nominal one does here).  The tile-conv
+// family is declined as a whole - also its 32 -> 64 and 64 -> 64 members, which run on igemm_wgrad_dma_kernel today (tileconv.hip):
+// conservative, and gwd_conv_wgrad refuses exactly what this declines, so a bias is summed once or refused, never dropped.
+extern "C" int gwd_conv_wgrad_takes_bias(const gwd_conv_desc *d, int32_t batched) {
+    if (check_desc(d) || d->dtype != GWD_BF16 || d->scale) return 0;
+    if (gwd_thin_conv_wgrad_accepts(d) || gwd_tile_conv_wgrad_family(d)) return 0;
+    return plan_wgrad(*d, dma_enabled(), batched != 0, 256).family == WgradFamily::DMA ? 1 : 0;
+}
+
 extern "C" int gwd_conv_wgrad(const gwd_conv_desc *d, float *dw, void *stream) {
     int rc = check_desc(d);
     if (rc) return rc;
     if (!dw) return -1;
+    if (d->dbias && !gwd_conv_wgrad_takes_bias(d, 0)) return -4;      // no kernel of this descriptor's family sums the bias: never dropped
     if (trace_conv()) trace_line("wgrad", d);
     if (gwd_thin_conv_wgrad(d, dw, (hipStream_t)stream) || gwd_tile_conv_wgrad(d, dw, (hipStream_t)stream)) {
         GWD_CHECK_LAUNCH();
@@ -2419,6 +2466,7 @@ extern "C" int gwd_conv_wgrad_batch(const gwd_conv_desc *descs, float *const *dw
         const int rc = check_desc(descs + i);
         if (rc) return rc;
         if (!dws[i]) return -1;
+        if (descs[i].dbias && !gwd_conv_wgrad_takes_bias(descs + i, 1)) return -4;
     }
     hipStream_t s = (hipStream_t)stream;
     WgradCollector coll(s);

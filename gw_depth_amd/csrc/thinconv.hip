@@ -216,8 +216,13 @@ int gwd_thin_conv_forward(const gwd_conv_desc *d, hipStream_t s) {
     return 0;
 }
 
+// the acceptance test of gwd_thin_conv_wgrad alone (gwd_conv_wgrad_takes_bias asks without launching)
+bool gwd_thin_conv_wgrad_accepts(const gwd_conv_desc *d) {
+    return thin_common(d) && d->gather == GWD_GATHER_CONV && d->Cin == C && (d->Cout == 1 || d->Cout == 2) && !d->scale;   // scaled gradients: igemm
+}
+
 int gwd_thin_conv_wgrad(const gwd_conv_desc *d, float *dw, hipStream_t s) {
-    if (!thin_common(d) || d->gather != GWD_GATHER_CONV || d->Cin != C || (d->Cout != 1 && d->Cout != 2) || d->scale) return 0;   // scaled gradients: igemm
+    if (!gwd_thin_conv_wgrad_accepts(d)) return 0;
     const int tiles = d->B * ((d->Hi + TILE - 1) / TILE) * ((d->Wi + TILE - 1) / TILE);
     constexpr int cap = 1024;                                          // every workgroup flushes its 288 / 576 sums with atomics onto the same addresses
     const int grid = tiles < cap ? tiles : cap;                        // <= 4 workgroups (34 KiB LDS each) per CU, one round

@@ -400,15 +400,27 @@ int gwd_tile_conv_forward(const gwd_conv_desc *d, hipStream_t s) {
 }
 
 // gwd_conv_wgrad's thin-channel case (desc.x = layer input, desc.y = output gradient, Cin = x channels, Cout = gy channels)
+// The weight gradients this file is in charge of: 3x3 / stride 1 / pad 1 over 32- or 64-channel maps of >= 131072 pixels, plain or 2x
+// up-sampled.  Of these tconv_wgrad_kernel runs the ones with 32 output-gradient channels today (the TW_ list below); x -> 64 is handed
+// on to the generic kernels.  gwd_conv_wgrad_takes_bias declines the WHOLE family, so its answer - and the caller's routing of the bias
+// gradient - does not depend on which member has its tile kernel yet.
+bool gwd_tile_conv_wgrad_family(const gwd_conv_desc *d) {
+    using namespace tconv;
+    if (!enabled() || d->dtype != GWD_BF16 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1) return false;
+    if ((long)d->B * d->Ho * d->Wo < 131072 || (long)d->B * d->Ho * d->Wo >= (1L << 31)) return false;
+    if (((uintptr_t)d->x | (uintptr_t)d->y) % 16) return false;
+    if (d->gather == GWD_GATHER_UPSAMPLED) {
+        if (d->Hv != 2 * d->Hi || d->Wv != 2 * d->Wi || d->Ho != d->Hv || d->Wo != d->Wv) return false;
+    } else if (d->gather != GWD_GATHER_CONV || d->Ho != d->Hi || d->Wo != d->Wi) return false;
+    return (d->Cin == 32 || d->Cin == 64) && (d->Cout == 32 || d->Cout == 64);
+}
+// the acceptance test of gwd_tile_conv_wgrad alone
+static bool gwd_tile_conv_wgrad_accepts(const gwd_conv_desc *d) { return gwd_tile_conv_wgrad_family(d) && d->Cout == 32; }
+
 int gwd_tile_conv_wgrad(const gwd_conv_desc *d, float *dw, hipStream_t s) {
     using namespace tconv;
-    if (!enabled() || d->dtype != GWD_BF16 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1) return 0;
-    if ((long)d->B * d->Ho * d->Wo < 131072 || (long)d->B * d->Ho * d->Wo >= (1L << 31)) return 0;
-    if (((uintptr_t)d->x | (uintptr_t)d->y) % 16) return 0;
+    if (!gwd_tile_conv_wgrad_accepts(d)) return 0;
     const bool up = d->gather == GWD_GATHER_UPSAMPLED;
-    if (up) {
-        if (d->Hv != 2 * d->Hi || d->Wv != 2 * d->Wi || d->Ho != d->Hv || d->Wo != d->Wv) return 0;
-    } else if (d->gather != GWD_GATHER_CONV || d->Ho != d->Hi || d->Wo != d->Wi) return 0;
     const int cx = d->Cin, cg = d->Cout;
 #define TW_(CX_, CG_)                                                                               \
     if (cx == CX_ && cg == CG_) return up ? launch_wgrad<CX_, CG_, true>(d, dw, s) : launch_wgrad<CX_, CG_, false>(d, dw, s);

@@ -29,6 +29,7 @@ ENTRY_POINTS = [
     "gwd_inorm_gelu_forward", "gwd_inorm_gelu_backward", "gwd_weight_prep_batch",
     "gwd_point_sample_forward", "gwd_point_sample_backward", "gwd_act_backward_colsum", "gwd_resample_backward_sep",
     "gwd_softmax_masked_forward", "gwd_softmax_scaled_backward", "gwd_query_workspace", "gwd_eval_accumulate", "gwd_colsum_batch", "gwd_conv_wgrad_batch",
+    "gwd_conv_wgrad_takes_bias",
     "gwd_plane_loss_forward", "gwd_plane_loss_backward", "gwd_collate",
     "gwd_anchor_depth_forward", "gwd_anchor_depth_backward", "gwd_mha_flash_forward", "gwd_mha_flash_backward",
     "gwd_ref_scores_forward", "gwd_ref_scores_backward", "gwd_ref_mix_forward", "gwd_ref_mix_backward", "gwd_unpad_add_batch", "gwd_stem_pack", "gwd_stem_forward", "gwd_pos_sine", "gwd_silog_finalize", "gwd_psp_pool_forward", "gwd_psp_pool_backward",
@@ -48,7 +49,8 @@ class ConvDesc(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("B", "Hi", "Wi", "Cin", "Ho", "Wo", "Cout", "KH", "KW", "stride", "pad",
                                               "gather", "Hv", "Wv", "act")] + \
                [("act_scale", ctypes.c_float), ("dtype", ctypes.c_int32), ("gate_act", ctypes.c_int32),
-                ("ln_mean", ctypes.c_void_p), ("ln_rstd", ctypes.c_void_p), ("ln_C", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("ln_mean", ctypes.c_void_p), ("ln_rstd", ctypes.c_void_p), ("ln_C", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("dbias", ctypes.c_void_p)]
 
 
 class BmmDesc(ctypes.Structure):
@@ -165,6 +167,7 @@ class HipLibrary:
         L.gwd_act_backward.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, i32, vp]
         L.gwd_colsum.argtypes = [vp, vp, i64, i32, i32, vp]
         L.gwd_conv_wgrad_batch.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_void_p), i32, vp]
+        L.gwd_conv_wgrad_takes_bias.argtypes = [ctypes.POINTER(ConvDesc), i32]
         L.gwd_plane_loss_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]
         L.gwd_plane_loss_backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp]
         L.gwd_collate.argtypes = [ctypes.POINTER(ImageJob), i32, i32, i32, ctypes.POINTER(ctypes.c_float),
@@ -269,7 +272,7 @@ class HipLibrary:
     @staticmethod
     def _desc(x, w, y, dims, z=None, scale=None, shift=None, residual=None, stride=1, pad=0,
               gather=GATHER_CONV, virt=(0, 0), act=ACT_NONE, act_scale=1.0, mult=None, gate=None, gate_act=ACT_NONE, ln=None,
-              zero_page=True):
+              zero_page=True, dbias=None):
         B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW = dims
         d = ConvDesc()
         d.x, d.w, d.y, d.z = _ptr(x), _ptr(w), _ptr(y), _ptr(z)
@@ -282,6 +285,7 @@ class HipLibrary:
         d.act, d.act_scale, d.dtype = act, act_scale, dtype_code(x)
         if ln is not None:                              # ConvLn mode: (mean, rstd, real channel count), gwd_conv_desc.ln_*
             d.ln_mean, d.ln_rstd, d.ln_C = _ptr(ln[0]), _ptr(ln[1]), int(ln[2])
+        d.dbias = _ptr(dbias)                           # weight gradient only: the bias gradient rides along (gwd_conv_desc.dbias)
         return d
 
     def conv_forward(self, x, w, y, dims, **kw):
@@ -299,8 +303,16 @@ class HipLibrary:
         self._check(rc, "gwd_conv_forward")
 
     def conv_wgrad(self, x, gy, dw, dims, **kw):
+        """kw as for conv_forward, plus dbias: fp32 [Cout], the column sums of gy are ACCUMULATED into it by the weight-gradient kernel
+        itself - only where conv_wgrad_takes_bias answers True, else the call fails with -4 (nothing launched)."""
         d = self._desc(x, None, gy, dims, **kw)
-        self._check(self.lib.gwd_conv_wgrad(ctypes.byref(d), _ptr(dw), self._stream(x, gy, dw)), "gwd_conv_wgrad")
+        self._check(self.lib.gwd_conv_wgrad(ctypes.byref(d), _ptr(dw), self._stream(x, gy, dw, kw.get("dbias"))), "gwd_conv_wgrad")
+
+    def conv_wgrad_takes_bias(self, x, gy, dims, batched, **kw):
+        """gwd_conv_wgrad_takes_bias: whether the kernel that conv_wgrad (batched: conv_wgrad_batch) selects for this problem sums the
+        bias gradient too.  Host logic only."""
+        d = self._desc(x, None, gy, dims, **kw)
+        return self.lib.gwd_conv_wgrad_takes_bias(ctypes.byref(d), 1 if batched else 0) == 1
 
     def conv_wgrad_batch(self, jobs):
         """jobs: tuples (x, gy, dw, dims, kw) as for conv_wgrad; one library call, grouped launches (gwd_conv_wgrad_batch)."""
@@ -310,7 +322,7 @@ class HipLibrary:
         for i, (x, gy, dw, dims, kw) in enumerate(jobs):
             descs[i] = self._desc(x, None, gy, dims, **kw)
             dws[i] = _ptr(dw)
-            ts += [x, gy, dw]
+            ts += [x, gy, dw, kw.get("dbias")]
         self._check(self.lib.gwd_conv_wgrad_batch(descs, dws, len(jobs), self._stream(*ts)), "gwd_conv_wgrad_batch")
 
     def weight_prep(self, w, row_scale, w_fwd, w_dgrad, N, taps, C, dtype):

@@ -211,6 +211,15 @@ class ColsumQueue:
 COLSUMS = ColsumQueue()
 
 
+def _both(first, second):
+    """One hook out of two (either may be None): a weight-gradient job that carries the layer's bias gradient fires both."""
+    def fire():
+        if first is not None:
+            first()
+        second()
+    return fire
+
+
 class WgradQueue:
     """Weight gradients that accumulate into the flat gradient buffer, handed to the library WGRAD_BATCH at a time
     (gwd_conv_wgrad_batch runs the small plain-GEMM ones of a batch as one grouped launch).  Same life cycle as
@@ -655,7 +664,15 @@ class _ConvFn(torch.autograd.Function):
                 WGRADS.add(dv, x, D, (B, Ho, Wo, Cout, Hi, Wi, Cin, 4, 4), dict(stride=2, pad=1), fold)
             elif w_sink is not None:
                 # the kernel ACCUMULATES (fp32 atomics): add straight into the flat gradient buffer, no temporary
-                WGRADS.add(x, dv, w_sink[0], dims, dict(stride=stride, pad=pad, gather=gather, virt=vv, scale=row_scale), w_sink[1])
+                kw, hook = dict(stride=stride, pad=pad, gather=gather, virt=vv, scale=row_scale), w_sink[1]
+                if (has_bias and ctx.needs_input_grad[2] and not bias_done and b_sink is not None and x.is_cuda
+                        and lib.conv_wgrad_takes_bias(x, dv, dims, WGRADS.active, **kw)):
+                    # the weight-gradient kernel stages every element of dv anyway: it sums the bias gradient from its dY tiles, and the
+                    # column-sum pass over the same map below is not run; both hooks fire once the job has been issued
+                    kw["dbias"], bias_done = b_sink[0], True
+                    if b_sink[1] is not None:
+                        hook = _both(w_sink[1], b_sink[1])
+                WGRADS.add(x, dv, w_sink[0], dims, kw, hook)
             else:
                 gw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
                 lib.conv_wgrad(x, dv, gw, dims, stride=stride, pad=pad, gather=gather, virt=vv, scale=row_scale)

@@ -71,6 +71,11 @@ typedef struct {
     float *ln_rstd;
     int32_t ln_C;
     int32_t reserved;
+    /* gwd_conv_wgrad / gwd_conv_wgrad_batch only (ignored elsewhere), may be NULL: dbias[Cout] fp32, ACCUMULATED (atomics, caller       */
+    /* zeroes): dbias[n] += sum over the output pixels of y[pixel][n] - the bias gradient of the layer, from the dY tiles the weight  */
+    /* gradient stages anyway instead of a gwd_colsum pass over the same map.  Only the LDS-DMA weight-gradient kernels do it: ask    */
+    /* gwd_conv_wgrad_takes_bias first; a descriptor it answers 0 for is refused with -4 (nothing launched, never silently dropped).  */
+    float *dbias;
 } gwd_conv_desc;
 
 int gwd_version(void);
@@ -107,6 +112,12 @@ int gwd_conv_wgrad(const gwd_conv_desc *d, float *dw, void *stream);
  * kernel shape as ONE launch - the weight gradients of the ~230 Linear / 1x1 layers of a train step are 10-60 us
  * launches of 16-400 workgroups that cannot overlap inside one stream.  Nothing in descs / dws must outlive the call. */
 int gwd_conv_wgrad_batch(const gwd_conv_desc *descs, float *const *dws, int32_t n, void *stream);
+/* 1 if the kernel gwd_conv_wgrad (batched != 0: gwd_conv_wgrad_batch) selects for this descriptor accumulates d->dbias, else 0: the
+ * LDS-DMA family only (bf16, zero page, channel counts in whole 16-byte vectors), without d->scale (a bias under a folded FrozenBN
+ * does not exist on this path, and the per-row multiplier must not reach the bias sum).  The tile-conv layers (3x3 / stride 1 over
+ * 32- / 64-channel maps of >= 131072 pixels) are declined as a family, whichever kernel takes the member today.  Pure host logic on the descriptor's shape
+ * fields, dtype and pointer alignment: launches nothing, touches no device; d->dbias itself is not looked at.                  */
+int gwd_conv_wgrad_takes_bias(const gwd_conv_desc *d, int32_t batched);
 
 /* w (fp32 [N][taps][C]), optionally multiplied by row_scale[N] (a frozen BatchNorm folded into the
  * convolution) -> w_fwd (dtype, same layout; may be NULL) and w_dgrad (dtype, [C][taps][N]; may be
