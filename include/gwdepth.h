@@ -183,7 +183,8 @@ int gwd_softmax_backward(const void *gy, const void *y, void *gx, int64_t rows, 
                          void *stream);
 /* Attention softmax with the score scaling and the key-padding mask folded in (src/models/multi_head_attention.py:
  * 329-352: q * scaling, masked_fill(-inf), softmax): y = softmax_row(scale * x + mask), key_mask uint8
- * [rows / rows_per_mask][L] (nonzero = key excluded) or NULL.  Backward: gx = scale * y * (gy - <y, gy>).       */
+ * [rows / rows_per_mask][L] (nonzero = key excluded) or NULL.  Backward: gx = scale * y * (gy - <y, gy>).
+ * A row whose keys are all excluded (or all -inf) is NaN in every element, as it is in the reference.          */
 int gwd_softmax_masked_forward(const void *x, const uint8_t *key_mask, void *y, int64_t rows, int32_t L, int64_t rows_per_mask,
                                float scale, int32_t dtype, void *stream);
 int gwd_softmax_scaled_backward(const void *gy, const void *y, void *gx, int64_t rows, int32_t L, float scale, int32_t dtype,

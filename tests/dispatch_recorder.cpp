@@ -1,6 +1,6 @@
 // Host-only recorder of the convolution dispatch (tests/test_conv_dispatch.py builds and runs it).
 // Links csrc/igemm.o, thinconv.o and tileconv.o WITHOUT the HIP runtime: the dozen runtime symbols those objects need are the stubs
-// below, hipLaunchKernel among them, which prints instead of launching.  Walks a grid of descriptors through gwd_conv_forward,
+// of tests/hip_stubs.h, hipLaunchKernel among them, which prints instead of launching.  Walks a grid of descriptors through gwd_conv_forward,
 // gwd_conv_wgrad and gwd_conv_wgrad_batch (and the three weight-copy entry points) and prints one line per call:
 //   <call> <descriptor> rc=<return code> { | <mangled kernel> <grid> <block> <dynamic LDS> <int arguments> }
 // The output depends on the host logic of the three objects and on the stubbed CU count (256) only.
@@ -16,65 +16,13 @@
 #include <vector>
 
 #include "gwdepth.h"
-
-struct dim3 { unsigned x, y, z; };
-typedef int hipError_t;
-typedef struct ihipStream_t *hipStream_t;
+#include "hip_stubs.h"
 
 namespace {
-struct Kernel { const void *host; const char *name; };
-Kernel g_kernels[1024];                                   // filled by the objects' static constructors: plain storage, no constructor of its own
-int g_n_kernels = 0;
-dim3 g_grid, g_block;
-size_t g_lds;
-std::string g_line;                                       // the record of the call in flight
-
-const char *kernel_name(const void *host) {
-    for (int i = 0; i < g_n_kernels; ++i)
-        if (g_kernels[i].host == host) return g_kernels[i].name;
-    return "?";
-}
 // positions of the scalar int arguments that follow the descriptor (and dw), by kernel
-struct IntArgs { const char *kernel; int first, count; };
 const IntArgs INT_ARGS[] = {{"igemm_dma_kernel", 1, 2},  {"gemm_ksplit_kernel", 1, 1}, {"igemm_wgrad_dma_kernel", 2, 1}, {"igemm_wgrad_kernel", 2, 1},
                             {"wgrad_taps_kernel", 2, 2}, {"tconv_fwd_kernel", 1, 3},   {"tconv_wgrad_kernel", 2, 3},     {"thin_wgrad_kernel", 2, 1}};
 }  // namespace
-
-extern "C" {
-void **__hipRegisterFatBinary(const void *) { static void *handle; return &handle; }
-void __hipUnregisterFatBinary(void **) {}
-void __hipRegisterFunction(void **, const void *host, char *, const char *name, unsigned, void *, void *, void *, void *, int *) {
-    if (g_n_kernels < 1024) g_kernels[g_n_kernels++] = {host, name};
-}
-void __hipRegisterVar(void **, void *, char *, const char *, int, size_t, int, int) {}
-unsigned __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, hipStream_t) {
-    g_grid = grid, g_block = block, g_lds = lds;
-    return 0;
-}
-hipError_t __hipPopCallConfiguration(dim3 *grid, dim3 *block, size_t *lds, hipStream_t *stream) {
-    *grid = g_grid, *block = g_block, *lds = g_lds, *stream = nullptr;
-    return 0;
-}
-hipError_t hipLaunchKernel(const void *host, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t) {
-    const char *name = kernel_name(host);
-    char buf[96];
-    snprintf(buf, sizeof buf, " %u,%u,%u %u %zu", grid.x, grid.y, grid.z, block.x, lds);
-    g_line += " | ";
-    g_line += name;
-    g_line += buf;
-    for (const IntArgs &ia : INT_ARGS)
-        if (strstr(name, ia.kernel))
-            for (int i = 0; i < ia.count; ++i) {
-                snprintf(buf, sizeof buf, "%c%d", i ? ',' : ' ', *(const int *)args[ia.first + i]);
-                g_line += buf;
-            }
-    return 0;
-}
-hipError_t hipGetLastError() { return 0; }
-hipError_t hipFuncSetAttribute(const void *, int, int) { return 0; }
-hipError_t hipGetDevice(int *dev) { *dev = 0; return 0; }
-hipError_t hipDeviceGetAttribute(int *value, int, int) { *value = 256; return 0; }
-}
 
 namespace {
 // fake device pointers: never dereferenced on the host, 16-byte aligned (tileconv.hip looks at the alignment)
@@ -315,6 +263,7 @@ int replay_stdin() {
 int main(int argc, char **argv) {
     static char out_buf[1 << 20];
     setvbuf(stdout, out_buf, _IOFBF, sizeof out_buf);
+    g_int_args = INT_ARGS, g_n_int_args = (int)(sizeof INT_ARGS / sizeof INT_ARGS[0]);
     if (argc > 1) return strcmp(argv[1], "--stdin") == 0 ? replay_stdin() : 2;
     record_forward();
     std::vector<gwd_conv_desc> pool;
