@@ -342,6 +342,26 @@ def polygon_lines(shapes):
     return np.array(lines), np.array(ids), centres
 
 
+def _item_targets(h, w, shapes):
+    """Polygon JSON -> (lines (n,4), poly_ids (n,), centres (n,2)) clamped to the (h, w) frame: the head of an item's assembly."""
+    ln, ids, cs = polygon_lines(shapes)
+    lines = torch.as_tensor(ln, dtype=torch.float32).reshape(-1, 4)
+    centres = torch.as_tensor(cs, dtype=torch.float32).reshape(-1, 2)
+    ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
+    if len(lines) > 0:
+        lines = torch.minimum(torch.maximum(lines, torch.zeros(4)), torch.tensor([w, h, w, h], dtype=torch.float32))
+        centres = torch.minimum(torch.maximum(centres, torch.zeros(2)), torch.tensor([w, h], dtype=torch.float32))
+    return lines, ids, centres
+
+
+def _item_target(lines, ids, centres, image_id, h, w, fh, fw, with_center):
+    """The per-item tail: lines / centres as fractions of the final (fh, fw) size and the target dict."""
+    lines, centres = normalize_lines(lines, fw, fh, centres)
+    return {"lines": torch.cat([lines, centres], dim=1) if with_center else lines,
+            "labels": torch.zeros(lines.shape[0], dtype=torch.int64), "poly_ids": ids,
+            "image_id": torch.tensor([image_id]), "orig_size": torch.as_tensor([h, w]), "size": torch.as_tensor([fh, fw])}
+
+
 def assemble_item(rgb, depth_mm, labels, shapes, image_id, with_center=True, params=None, mean=MEAN, std=STD):
     """One dataset item from DECODED arrays - DataLoadPreprocess.__getitem__ without the file handling
     (glassrgbd_norhint.py:236-299 with ConvertLinePolysToMask :121-148): polygon JSON -> line targets (clamped to the frame),
@@ -351,21 +371,27 @@ def assemble_item(rgb, depth_mm, labels, shapes, image_id, with_center=True, par
     one launch.  rgb uint8 (h,w,3), depth_mm integer (h,w), labels uint8 (h,w): device tensors.
     Returns (rgb, depth_mm, labels, target) with target = {lines, labels, poly_ids, image_id, orig_size, size}."""
     h, w = int(rgb.shape[0]), int(rgb.shape[1])
-    ln, ids, cs = polygon_lines(shapes)
-    lines = torch.as_tensor(ln, dtype=torch.float32).reshape(-1, 4)
-    centres = torch.as_tensor(cs, dtype=torch.float32).reshape(-1, 2)
-    ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1)
-    if len(lines) > 0:
-        lines = torch.minimum(torch.maximum(lines, torch.zeros(4)), torch.tensor([w, h, w, h], dtype=torch.float32))
-        centres = torch.minimum(torch.maximum(centres, torch.zeros(2)), torch.tensor([w, h], dtype=torch.float32))
+    lines, ids, centres = _item_targets(h, w, shapes)
     if params is not None:
         rgb, depth_mm, labels, lines, ids, centres = DeviceAugment.apply(rgb, depth_mm, labels, lines, params, poly_ids=ids, centres=centres)
     fh, fw = int(rgb.shape[0]), int(rgb.shape[1])
-    lines, centres = normalize_lines(lines, fw, fh, centres)
-    target = {"lines": torch.cat([lines, centres], dim=1) if with_center else lines,
-              "labels": torch.zeros(lines.shape[0], dtype=torch.int64), "poly_ids": ids,
-              "image_id": torch.tensor([image_id]), "orig_size": torch.as_tensor([h, w]), "size": torch.as_tensor([fh, fw])}
-    return rgb, depth_mm, labels, target
+    return rgb, depth_mm, labels, _item_target(lines, ids, centres, image_id, h, w, fh, fw, with_center)
+
+
+def assemble_batch(items, params, device="cuda", dtype=torch.float32, with_center=True):
+    """A whole batch from DECODED arrays: assemble_item for every item and device_collate, with the transform chains of all
+    items in DeviceAugment.apply_batch's fixed number of launches.  items: list (<= 16) of (rgb, depth_mm, labels, shapes,
+    image_id) as assemble_item takes them; params: one DeviceAugment.params dict (or None = no step) per item.
+    Returns (the batch dict of device_collate, the list of target dicts)."""
+    if len(items) != len(params):
+        raise ValueError("one params entry per item")
+    sizes = [(int(it[0].shape[0]), int(it[0].shape[1])) for it in items]
+    tg = [_item_targets(h, w, it[3]) for (h, w), it in zip(sizes, items)]
+    out = DeviceAugment.apply_batch([it[:3] for it in items], [t[0] for t in tg], [p if p is not None else {"flip": None, "steps": []} for p in params],
+                                    poly_ids=[t[1] for t in tg], centres=[t[2] for t in tg])
+    targets = [_item_target(o[3], o[4], o[5], it[4], h, w, int(o[0].shape[0]), int(o[0].shape[1]), with_center)
+               for o, it, (h, w) in zip(out, items, sizes)]
+    return device_collate([o[:3] for o in out], device=device, dtype=dtype), targets
 
 
 class DeviceAugment:
@@ -455,6 +481,33 @@ class DeviceAugment:
             return rgb, depth_mm, labels, lines, poly_ids, centres
         return rgb, depth_mm, labels, lines, keep
 
+    @staticmethod
+    def apply_batch(frames, lines, params, poly_ids=None, centres=None):
+        """apply() for a whole batch in a number of launches that does not depend on its size.  frames: list of 1..16
+        (rgb, depth_mm | None, labels | None) device tensors of any sizes, lines / params (and poly_ids / centres, when given):
+        lists of the same length.  Returns the list of the tuples apply() returns, value for value.
+
+        The batch is planned on the host first - every coefficient, bound and index table of every frame lands in one pinned
+        int32 buffer, uploaded with one asynchronous copy - and then launched: at most four grouped resample launches (first and
+        second BILINEAR resize, horizontal and vertical), one grouped gather (depth, labels and the RGB frames that are flipped /
+        cropped / copied but never resized), and per jitter slot one grouped adjustment in place plus one luma-sum launch where a
+        frame's adjustment is a contrast.  A chain may hold at most two size-changing resizes (the reference's chains hold two)."""
+        n = len(frames)
+        if not 0 < n <= hip.AUGMENT_BATCH:
+            raise ValueError("1..%d frames per call" % hip.AUGMENT_BATCH)
+        if len(lines) != n or len(params) != n or any(x is not None and len(x) != n for x in (poly_ids, centres)):
+            raise ValueError("one lines / params (/ poly_ids / centres) entry per frame")
+        lib = hip.library()
+        plan = _BatchPlan(frames[0][0].device)
+        out = []
+        for f, ((rgb, depth_mm, labels), p) in enumerate(zip(frames, params)):
+            images = plan.add_frame(rgb, depth_mm, labels, p)
+            targets = _transform_targets(int(rgb.shape[0]), int(rgb.shape[1]), lines[f], p, None if poly_ids is None else poly_ids[f],
+                                         None if centres is None else centres[f])
+            out.append(images + targets)
+        plan.launch(lib)
+        return out
+
 
 # --- third slice: the photometric jitter (transforms_depth.py:551-600) ------------------------------------------------------------
 def hue_shift(hue_factor):
@@ -486,3 +539,202 @@ def jitter_params(rng, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.4):
     lo_hi = [(max(0.0, 1 - brightness), 1 + brightness), (max(0.0, 1 - contrast), 1 + contrast), (max(0.0, 1 - saturation), 1 + saturation),
              (-hue, hue)]
     return [(names[i], rng.uniform(*lo_hi[i])) for i in order]
+
+
+# --- fourth slice: the augmentation of a whole batch in a fixed number of launches (DeviceAugment.apply_batch) ---------------------
+import functools
+
+
+@functools.lru_cache(maxsize=256)
+def _bilinear_tables_cached(in_size, out_size):
+    tabs = bilinear_tables(in_size, out_size)
+    for t in tabs:
+        t.setflags(write=False)
+    return tabs
+
+
+@functools.lru_cache(maxsize=256)
+def _nearest_table_cached(in_size, out_size):
+    t = nearest_table(in_size, out_size)
+    t.setflags(write=False)
+    return t
+
+
+def upload_tables(host, device):
+    """The one host-to-device copy of apply_batch: the batch's table buffer (pinned when the target is a GPU), asynchronously."""
+    return host.to(device, non_blocking=True)
+
+
+def _transform_targets(h, w, lines, p, poly_ids, centres):
+    """The host arithmetic of DeviceAugment.apply on one frame's line targets, without the images: (lines, keep), or with the
+    polygon bookkeeping (lines, poly_ids, centres).  tests/test_augment_batch.py pins it to apply()."""
+    hf, vf = p["flip"] == "h", p["flip"] == "v"
+    lines = lines.clone().float()
+    keep = torch.ones(lines.shape[0], dtype=torch.bool)
+    full = poly_ids is not None
+    if full:
+        poly_ids, centres = poly_ids.clone(), centres.clone().float()
+    if hf:
+        lines = hflip_lines(lines, w)
+        if full:
+            centres = centres * torch.as_tensor([-1.0, 1.0]) + torch.as_tensor([float(w), 0.0])
+    if vf:
+        lines = vflip_lines(lines, h)
+        if full:
+            centres = centres * torch.as_tensor([1.0, -1.0]) + torch.as_tensor([0.0, float(h)])
+    for step in p["steps"]:
+        if step[0] == "resize":
+            oh, ow = resized_shape(w, h, step[1], step[2])
+            lines = resize_lines(lines, w, h, ow, oh)
+            if full:
+                centres = centres * torch.as_tensor([float(ow) / float(w), float(oh) / float(h)])
+            h, w = oh, ow
+        else:
+            if full:
+                lines, poly_ids, centres, k = crop_targets(lines, poly_ids, centres, step[1])
+            else:
+                lines, k = crop_lines(lines, step[1])
+            idx = torch.nonzero(keep).flatten()
+            keep = torch.zeros_like(keep)
+            keep[idx[k]] = True
+            h, w = step[1][2], step[1][3]
+    return (lines, poly_ids, centres) if full else (lines, keep)
+
+
+class _BatchPlan:
+    """The launches of one apply_batch call: job lists per grouped launch and the table buffer they index."""
+
+    def __init__(self, device):
+        self.device = device
+        self.parts, self.n_tables = [], 0
+        self.resample = [[[], []], [[], []]]          # [stage][0 = horizontal, 1 = vertical] -> resample_u8_pass_batch jobs
+        self.gather = []                              # gather2d_batch jobs
+        self.slots = [[] for _ in range(4)]           # jitter slot -> color_adjust_batch jobs
+
+    def table(self, a):
+        """Appends an int32 table to the buffer; returns its offset."""
+        a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        off = self.n_tables
+        self.parts.append(a)
+        self.n_tables += a.size
+        return off
+
+    def resize_rgb(self, stage, src, rs, ymap, xmap, in_size, out_size, window):
+        """One BILINEAR resize of the (in_h, in_w) image read from `src` through the index maps (base, step) per axis, of which
+        only the window (i, j, ch, cw) of the (oh, ow) result is produced: the tables are sliced to the window's rows and
+        columns - every output pixel is independent, so this is the resize followed by the crop.  Returns the dense window."""
+        (in_h, in_w), (oh, ow), (i, j, ch, cw) = in_size, out_size, window
+        (yb, ys), (xb, xs) = ymap, xmap
+        need_h, need_v = ow != in_w, oh != in_h
+        C = src.shape[2]
+        if need_v:
+            bv, kv = _bilinear_tables_cached(in_h, oh)
+            bv, kv = bv[i:i + ch], kv[i:i + ch]
+        cur, cur_rs = src, rs
+        if not need_h:
+            xb += xs * j                              # the vertical pass alone reads the window's columns of the source
+        else:
+            bh, kh = _bilinear_tables_cached(in_w, ow)
+            bh, kh = bh[j:j + cw], kh[j:j + cw]
+            first, last = (int(bv[0, 0]), int(bv[-1, 0] + bv[-1, 1])) if need_v else (i, i + ch)   # only the rows that are read
+            tmp = torch.empty((last - first, cw, C), dtype=torch.uint8, device=self.device)
+            self.resample[stage][0].append((src, tmp, rs, self.table(bh), self.table(kh), kh.shape[1], xb, xs, yb + ys * first, ys))
+            if need_v:
+                bv = bv.copy()
+                bv[:, 0] -= first
+            cur, cur_rs, yb, ys, xb, xs = tmp, cw * C, 0, 1, 0, 1
+        if need_v:
+            out = torch.empty((ch, cw, C), dtype=torch.uint8, device=self.device)
+            self.resample[stage][1].append((cur, out, cur_rs, self.table(bv), self.table(kv), kv.shape[1], yb, ys, xb, xs))
+            return out
+        return cur
+
+    def add_frame(self, rgb, depth_mm, labels, p):
+        """Plans one frame; returns its (rgb, depth_mm, labels) outputs, filled in by launch()."""
+        h, w = int(rgb.shape[0]), int(rgb.shape[1])
+        if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.stride(2) != 1 or rgb.stride(1) != rgb.shape[2]:
+            raise ValueError("apply_batch: a uint8 (h,w,C) image or a row-window view of one expected")
+        for m in (depth_mm, labels):
+            if m is not None and (tuple(m.shape) != (h, w) or m.stride(1) != 1 or m.element_size() not in (1, 2, 4)):
+                raise ValueError("apply_batch: depth / labels are (h,w) maps of 1-, 2- or 4-byte elements")
+        hf, vf = p["flip"] == "h", p["flip"] == "v"
+        # NEAREST resizes, flips and crops compose into ONE index table per axis: source index of every final row / column
+        ytab = np.arange(h, dtype=np.int32)[::-1] if vf else np.arange(h, dtype=np.int32)
+        xtab = np.arange(w, dtype=np.int32)[::-1] if hf else np.arange(w, dtype=np.int32)
+        moved = hf or vf
+        # BILINEAR passes round to uint8 and do not compose: the RGB image goes resize by resize (stages), each reading its source
+        # through per-axis (base, step) maps that carry the flip and any crop in front of it
+        src, rs, ymap, xmap = rgb, rgb.stride(0), _flip_map(h, vf), _flip_map(w, hf)
+        pending, stage = None, 0                      # a resize whose window later crops may still shrink: [in, out, window]
+        for step in p["steps"]:
+            if step[0] == "resize":
+                oh, ow = resized_shape(w, h, step[1], step[2])
+                if (oh, ow) != (h, w):
+                    moved = True
+                    ytab = ytab[_nearest_table_cached(h, oh)] if oh != h else ytab
+                    xtab = xtab[_nearest_table_cached(w, ow)] if ow != w else xtab
+                    if pending is not None:
+                        if stage == 1:
+                            raise ValueError("apply_batch: at most two size-changing resizes per chain")
+                        src = self.resize_rgb(0, src, rs, ymap, xmap, *pending)
+                        rs, ymap, xmap, stage = src.stride(0), (0, 1), (0, 1), 1
+                    pending = [(h, w), (oh, ow), (0, 0, oh, ow)]
+                    h, w = oh, ow
+            else:
+                i, j, ch, cw = (int(v) for v in step[1])
+                if i < 0 or j < 0 or ch <= 0 or cw <= 0 or i + ch > h or j + cw > w:
+                    raise ValueError("apply_batch: crop window %r outside the %d x %d image" % (step[1], h, w))
+                moved = True
+                ytab, xtab = ytab[i:i + ch], xtab[j:j + cw]
+                if pending is not None:
+                    pi, pj = pending[2][:2]
+                    pending[2] = (pi + i, pj + j, ch, cw)
+                else:
+                    ymap, xmap = (ymap[0] + ymap[1] * i, ymap[1]), (xmap[0] + xmap[1] * j, xmap[1])
+                h, w = ch, cw
+        jitter = p.get("jitter") or []
+        tabs = None
+        if moved or (jitter and pending is None):
+            tabs = (self.table(ytab), self.table(xtab))
+
+        def gathered(m, elem_bytes, shape):
+            out = torch.empty(shape, dtype=m.dtype, device=self.device)
+            self.gather.append((m, out, m.stride(0) * m.element_size(), tabs[0], tabs[1], h, w, elem_bytes))
+            return out
+
+        if pending is not None:
+            rgb_out = self.resize_rgb(stage, src, rs, ymap, xmap, *pending)
+        elif tabs is not None:                        # never resized: flip / crop / the copy the jitter writes into = the same tables
+            rgb_out = gathered(rgb, rgb.shape[2], (h, w, rgb.shape[2]))
+        else:
+            rgb_out = rgb
+        depth_out = depth_mm if depth_mm is None or not moved else gathered(depth_mm, depth_mm.element_size(), (h, w))
+        labels_out = labels if labels is None or not moved else gathered(labels, labels.element_size(), (h, w))
+        if len(jitter) > len(self.slots):
+            raise ValueError("apply_batch: at most %d jitter adjustments per frame" % len(self.slots))
+        for slot, (name, f) in zip(self.slots, jitter):
+            slot.append((rgb_out, name, float(hue_shift(f)) if name == "hue" else float(f)))
+        return rgb_out, depth_out, labels_out
+
+    def launch(self, lib):
+        tables = None
+        if self.n_tables:
+            host = torch.empty(self.n_tables, dtype=torch.int32, pin_memory=self.device.type == "cuda")
+            np.concatenate(self.parts, out=host.numpy())
+            tables = upload_tables(host, self.device)
+        for stage in self.resample:
+            for axis, jobs in ((1, stage[0]), (0, stage[1])):
+                if jobs:
+                    lib.resample_u8_pass_batch(jobs, axis, jobs[0][1].shape[2], tables)
+        if self.gather:
+            lib.gather2d_batch(self.gather, tables)
+        sums = None
+        if any(name == "contrast" for slot in self.slots for _, name, _ in slot):
+            sums = torch.zeros((len(self.slots), hip.AUGMENT_BATCH), dtype=torch.int64, device=self.device)
+        for s, slot in enumerate(self.slots):
+            if not slot:
+                continue
+            contrast = any(name == "contrast" for _, name, _ in slot)
+            if contrast:                              # the frames' luma sums, from the images as they stand before the blend
+                lib.color_adjust_batch(slot, sums[s], sums_only=True)
+            lib.color_adjust_batch(slot, sums[s] if contrast else None)

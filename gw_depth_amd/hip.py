@@ -35,6 +35,7 @@ ENTRY_POINTS = [
     "gwd_ref_scores_forward", "gwd_ref_scores_backward", "gwd_ref_mix_forward", "gwd_ref_mix_backward", "gwd_unpad_add_batch", "gwd_stem_pack", "gwd_stem_forward", "gwd_pos_sine", "gwd_silog_finalize", "gwd_psp_pool_forward", "gwd_psp_pool_backward",
     "gwd_match_cost", "gwd_set_losses_forward", "gwd_set_losses_backward", "gwd_resample_u8_pass", "gwd_gather2d", "gwd_point_sample_backward_gather", "gwd_point_sample_framed_forward", "gwd_point_sample_framed_backward", "gwd_stride_place", "gwd_color_adjust", "gwd_bmm",
     "gwd_dense_postprocess", "gwd_line_postprocess", "gwd_line_score",
+    "gwd_resample_u8_pass_batch", "gwd_gather2d_batch", "gwd_color_adjust_batch",
 ]
 
 
@@ -98,6 +99,30 @@ class ImageJob(ctypes.Structure):
     """gwd_image_job (include/gwdepth.h)."""
     _fields_ = [("rgb", ctypes.c_void_p), ("depth_mm", ctypes.c_void_p), ("labels", ctypes.c_void_p),
                 ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+AUGMENT_BATCH = 16        # frames per grouped augmentation launch
+GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
+COLOR_ADJUST, COLOR_SUMS = 0, 1
+
+
+class ResampleJob(ctypes.Structure):
+    """gwd_resample_job (include/gwdepth.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("src_row_stride", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("bounds_off", "kk_off", "ksize", "n_out", "other", "base0", "step0", "base1", "step1",
+                                              "block0", "blocks")]
+
+
+class GatherJob(ctypes.Structure):
+    """gwd_gather_job (include/gwdepth.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("src_row_stride_bytes", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("ytab_off", "xtab_off", "oh", "ow", "elem_bytes", "block0", "blocks")]
+
+
+class ColorJob(ctypes.Structure):
+    """gwd_color_job (include/gwdepth.h)."""
+    _fields_ = [("rgb", ctypes.c_void_p), ("npix", ctypes.c_int64), ("mode", ctypes.c_int32), ("factor", ctypes.c_float),
+                ("block0", ctypes.c_int32), ("blocks", ctypes.c_int32)]
 
 
 class Strided(ctypes.Structure):
@@ -183,6 +208,9 @@ class HipLibrary:
         L.gwd_silog_finalize.argtypes = [vp, f32, f32, vp, vp]
         L.gwd_resample_u8_pass.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i32, i32, i32, i32, vp]
         L.gwd_gather2d.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, vp]
+        L.gwd_resample_u8_pass_batch.argtypes = [ctypes.POINTER(ResampleJob), i32, i32, i32, vp, i64, vp]
+        L.gwd_gather2d_batch.argtypes = [ctypes.POINTER(GatherJob), i32, vp, i64, vp]
+        L.gwd_color_adjust_batch.argtypes = [ctypes.POINTER(ColorJob), i32, vp, i32, vp]
         L.gwd_match_cost.argtypes = [vp] * 5 + [i32] * 6 + [f32, f32, vp]
         L.gwd_set_losses_forward.argtypes = [vp] * 9 + [f32] + [vp] * 4 + [i32] * 6 + [vp]
         L.gwd_set_losses_backward.argtypes = [vp] * 8 + [f32] + [vp] * 6 + [i32] * 6 + [vp]
@@ -804,6 +832,71 @@ class HipLibrary:
             raise ValueError("gather2d: int32 tables and a dense (oh, ow) output expected")
         self._check(self.lib.gwd_gather2d(_ptr_pitched(src), _ptr(dst), _ptr(ytab), _ptr(xtab), oh, ow, row_stride_bytes, elem_bytes,
                                           self._stream(src, dst, ytab, xtab)), "gwd_gather2d")
+
+    @staticmethod
+    def _check_tables(tables, what):
+        if tables.dtype != torch.int32 or tables.dim() != 1:
+            raise ValueError(what + ": one flat int32 table buffer expected")
+
+    def resample_u8_pass_batch(self, jobs, axis, C, tables):
+        """gwd_resample_u8_pass_batch: ONE launch for up to AUGMENT_BATCH resample_u8_pass calls of one axis and channel count.
+        jobs: (src, dst, row_stride, bounds_off, kk_off, ksize, base0, step0, base1, step1); bounds (n_out,2) and kk (n_out,ksize)
+        start at those int32 offsets of `tables`; n_out / other are read off the dense dst as in resample_u8_pass."""
+        self._check_tables(tables, "resample_u8_pass_batch")
+        if not 0 < len(jobs) <= AUGMENT_BATCH:
+            raise ValueError("resample_u8_pass_batch: 1..%d jobs per call" % AUGMENT_BATCH)
+        recs = (ResampleJob * len(jobs))()
+        ts = [tables]
+        for r, (src, dst, row_stride, bounds_off, kk_off, ksize, base0, step0, base1, step1) in zip(recs, jobs):
+            if src.dtype != torch.uint8 or dst.dtype != torch.uint8 or not dst.is_contiguous() or dst.dim() != 3 or dst.shape[2] != C:
+                raise ValueError("resample_u8_pass_batch: uint8 images with a dense (.., .., C) output expected")
+            n_out, other = (dst.shape[1], dst.shape[0]) if axis == 1 else (dst.shape[0], dst.shape[1])
+            if min(bounds_off, kk_off) < 0 or bounds_off + 2 * n_out > tables.numel() or kk_off + n_out * ksize > tables.numel():
+                raise ValueError("resample_u8_pass_batch: a table lies outside the table buffer")
+            r.src, r.dst, r.src_row_stride = src.data_ptr(), dst.data_ptr(), row_stride
+            r.bounds_off, r.kk_off, r.ksize, r.n_out, r.other = bounds_off, kk_off, ksize, n_out, other
+            r.base0, r.step0, r.base1, r.step1 = base0, step0, base1, step1
+            ts += [src, dst]
+        self._check(self.lib.gwd_resample_u8_pass_batch(recs, len(jobs), axis, C, _ptr(tables), tables.numel(), self._stream(*ts)),
+                    "gwd_resample_u8_pass_batch")
+
+    def gather2d_batch(self, jobs, tables):
+        """gwd_gather2d_batch: ONE launch for up to GATHER_BATCH gather2d calls.  jobs: (src, dst, row_stride_bytes, ytab_off,
+        xtab_off, oh, ow, elem_bytes) with the index tables at those int32 offsets of `tables`; dst dense."""
+        self._check_tables(tables, "gather2d_batch")
+        if not 0 < len(jobs) <= GATHER_BATCH:
+            raise ValueError("gather2d_batch: 1..%d jobs per call" % GATHER_BATCH)
+        recs = (GatherJob * len(jobs))()
+        ts = [tables]
+        for r, (src, dst, row_stride_bytes, ytab_off, xtab_off, oh, ow, elem_bytes) in zip(recs, jobs):
+            if not dst.is_contiguous() or dst.numel() * dst.element_size() != oh * ow * elem_bytes:
+                raise ValueError("gather2d_batch: a dense (oh, ow) output expected")
+            if min(ytab_off, xtab_off) < 0 or ytab_off + oh > tables.numel() or xtab_off + ow > tables.numel():
+                raise ValueError("gather2d_batch: a table lies outside the table buffer")
+            r.src, r.dst, r.src_row_stride_bytes = src.data_ptr(), dst.data_ptr(), row_stride_bytes
+            r.ytab_off, r.xtab_off, r.oh, r.ow, r.elem_bytes = ytab_off, xtab_off, oh, ow, elem_bytes
+            ts += [src, dst]
+        self._check(self.lib.gwd_gather2d_batch(recs, len(jobs), _ptr(tables), tables.numel(), self._stream(*ts)), "gwd_gather2d_batch")
+
+    def color_adjust_batch(self, jobs, sums, sums_only=False):
+        """gwd_color_adjust_batch: one ColorJitter adjustment IN PLACE on each of up to AUGMENT_BATCH uint8 (h,w,3) device images
+        in ONE launch.  jobs: (rgb, mode name | None = leave untouched, factor as color_adjust takes it); sums: int64 tensor with
+        one zeroed element per job when a job is a 'contrast' (else None).  sums_only=True is the companion launch that adds
+        each contrast job's luma sum to sums[job]; run it before the adjusting call."""
+        if not 0 < len(jobs) <= AUGMENT_BATCH:
+            raise ValueError("color_adjust_batch: 1..%d jobs per call" % AUGMENT_BATCH)
+        if sums is not None and (sums.dtype != torch.int64 or sums.numel() < len(jobs)):
+            raise ValueError("color_adjust_batch: sums is an int64 tensor with an element per job")
+        recs = (ColorJob * len(jobs))()
+        ts = [sums]
+        for r, (rgb, mode, factor) in zip(recs, jobs):
+            if rgb.dtype != torch.uint8 or rgb.shape[-1] != 3 or not rgb.is_contiguous():
+                raise ValueError("color_adjust_batch: dense uint8 (h,w,3) images expected")
+            r.rgb, r.npix = rgb.data_ptr(), rgb.numel() // 3
+            r.mode, r.factor = (-1 if mode is None else self.COLOR_MODES[mode]), float(factor)
+            ts.append(rgb)
+        self._check(self.lib.gwd_color_adjust_batch(recs, len(jobs), _ptr(sums), COLOR_SUMS if sums_only else COLOR_ADJUST,
+                                                    self._stream(*ts)), "gwd_color_adjust_batch")
 
     def match_cost(self, logits, lines, tgt_lines, tgt_labels, cost, w_line, w_class):
         """cost (L,B,Q,cap) of matcher.py:52-70 from logits (L,B,Q,K), lines (L,B,Q,D), padded targets (cap,D) / (cap,) int64."""

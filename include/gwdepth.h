@@ -616,12 +616,59 @@ int gwd_resample_u8_pass(const uint8_t *src, uint8_t *dst, const int32_t *bounds
 int gwd_gather2d(const void *src, void *dst, const int32_t *ytab, const int32_t *xtab, int32_t oh, int32_t ow,
                  int64_t src_row_stride_bytes, int32_t elem_bytes, void *stream);
 
+/* The same passes for a whole BATCH of frames, one launch each whatever the number of frames.  The job records are read on the
+ * host and travel in the kernel arguments; block0 / blocks are filled in by the library.  Every job's tables live at int32
+ * offsets inside ONE device buffer `tables` of table_len int32 values, which the caller uploads once per batch; an offset or
+ * extent beyond table_len returns -3.  Nothing else is uploaded, nothing is allocated, nothing synchronises.
+ * gwd_resample_u8_pass_batch: job i has exactly the meaning of gwd_resample_u8_pass(src, dst, tables + bounds_off,
+ *   tables + kk_off, ksize, axis, n_out, other, C, src_row_stride, base0, step0, base1, step1); axis and C (1..4, else -4) are
+ *   common to the launch, everything else differs per job.  n <= GWD_AUGMENT_BATCH.
+ * gwd_gather2d_batch: job i = gwd_gather2d(src, dst, tables + ytab_off, tables + xtab_off, oh, ow, src_row_stride_bytes,
+ *   elem_bytes) with the element width (1..4, else -4) per job; for 2- and 4-byte elements src, dst and the row stride are
+ *   multiples of the width.  n <= GWD_GATHER_BATCH (RGB, depth and labels of GWD_AUGMENT_BATCH frames).              */
+#define GWD_AUGMENT_BATCH 16
+#define GWD_GATHER_BATCH 48
+typedef struct {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t src_row_stride;
+    int32_t bounds_off, kk_off, ksize, n_out, other, base0, step0, base1, step1;
+    int32_t block0, blocks;   /* library-internal */
+} gwd_resample_job;
+typedef struct {
+    const void *src;
+    void *dst;
+    int64_t src_row_stride_bytes;
+    int32_t ytab_off, xtab_off, oh, ow, elem_bytes;
+    int32_t block0, blocks;   /* library-internal */
+} gwd_gather_job;
+int gwd_resample_u8_pass_batch(const gwd_resample_job *jobs, int32_t n, int32_t axis, int32_t C, const int32_t *tables,
+                               int64_t table_len, void *stream);
+int gwd_gather2d_batch(const gwd_gather_job *jobs, int32_t n, const int32_t *tables, int64_t table_len, void *stream);
+
 /* One adjustment of the reference's ColorJitter (src/datasets/transforms_depth.py:551-600) on a uint8 RGB image of npix pixels,
  * bit-exact with torchvision's PIL path: mode 0 brightness, 1 contrast, 2 saturation (Pillow ImageEnhance: Image.blend with a black /
  * mean-luma / luma degenerate image, factor >= 0), 3 hue (RGB -> HSV, H + shift with uint8 wrap-around, HSV -> RGB; here `factor` is
  * the SHIFT 0..255 = uint8(hue_factor * 255) as the caller's host arithmetic casts it: int(hue_factor * 255) & 255).  scratch: 8 bytes of device memory (the contrast mean's luma sum; may be NULL for the other modes).  Data-pipeline
  * entry point: not meant for HIP-graph capture (mode 1 clears its scratch with a memset node).                                     */
 int gwd_color_adjust(const uint8_t *rgb, uint8_t *out, uint64_t *scratch, int64_t npix, int32_t mode, float factor, void *stream);
+/* One adjustment on each of up to GWD_AUGMENT_BATCH frames in ONE launch, IN PLACE, with the arithmetic of gwd_color_adjust
+ * (mode and factor per job as there; mode -1 leaves the frame untouched).  The records travel in the kernel arguments.
+ * Contrast (mode 1) reads the frame's 64-bit luma sum from sums[job index].  phase GWD_COLOR_SUMS is the companion launch that
+ * ADDS the luma sum of every mode-1 job's image, as it stands, to sums[job index] (integer atomics: order-independent, so the
+ * mean stays bit-exact) and touches no pixel; the caller zeroes `sums` beforehand and runs it before phase GWD_COLOR_ADJUST
+ * whenever a job is a contrast.  sums may be NULL when no job is.  A phase with nothing to do launches nothing.  Data-pipeline
+ * entry point like gwd_color_adjust: not meant for HIP-graph capture.                                                    */
+#define GWD_COLOR_ADJUST 0
+#define GWD_COLOR_SUMS 1
+typedef struct {
+    uint8_t *rgb;             /* [npix][3], adjusted in place            */
+    int64_t npix;
+    int32_t mode;             /* 0..3 as gwd_color_adjust, -1 = skip     */
+    float factor;
+    int32_t block0, blocks;   /* library-internal                        */
+} gwd_color_job;
+int gwd_color_adjust_batch(const gwd_color_job *jobs, int32_t n, uint64_t *sums, int32_t phase, void *stream);
 
 /* Strided batched GEMM  C[b0][b1] (M x N) = alpha * A[b0][b1] (M x K) * B[b0][b1] (N x K)^T  (csrc/bmm.hip).
  * Every operand has inner stride 1; a_ld / b_ld / c_ld are the element strides of the outer matrix dimension, *_sb0 / *_sb1 those of
