@@ -25,7 +25,8 @@ def build_model(args):
     if cfg.aux_loss:
         for i in range(cfg.dec_layers - 1):
             weight_dict.update({f"loss_ce_{i}": 1, f"loss_line_{i}": cfg.line_loss_coef})
-    criterion = SetCriterion(1, weight_dict, cfg.eos_coef, ["lines_labels", "lines"], matcher)
+    criterion = SetCriterion(1, weight_dict, cfg.eos_coef, ["lines_labels", "lines"], matcher,
+                             label_loss_func=cfg.label_loss_func, label_loss_params=cfg.label_loss_params)
     device = torch.device(cfg.device) if (cfg.device != "cuda" or torch.cuda.is_available()) else None
     if device is not None:
         criterion.to(device)

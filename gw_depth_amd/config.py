@@ -39,6 +39,8 @@ class Config:
     with_dense = True
     with_plane_norm_loss = False
     plane_norm_loss_coef = 50.0          # src/args.py:81
+    label_loss_func = "cross_entropy"    # src/args.py:76-77; "focal_loss" with label_loss_params '{"gamma": 2.0}' (string or dict)
+    label_loss_params = "{}"
 
     def __init__(self, **kw):
         for k, v in kw.items():

@@ -2,6 +2,7 @@
 /root/reference/src/models/matcher.py).  The dense losses run on the fused HIP reductions; the line
 losses are a few hundred elements (latency class) and use torch tensor plumbing plus scipy's LSAP on
 the host exactly as the reference does."""
+import ast
 import os
 
 import torch
@@ -72,12 +73,47 @@ class HungarianMatcherLine(nn.Module):
         return self._solve(handle["host"][i], handle["sizes"])
 
 
+def focal_gamma(label_loss_func, label_loss_params):
+    """None for 'cross_entropy', gamma for 'focal_loss' (glassrgbd.py:149-152,167-172: the params are a dict or its string form, the
+    keywords of label_focal_loss(..., gamma=2.0))."""
+    if label_loss_func == "cross_entropy":
+        return None
+    if label_loss_func != "focal_loss":
+        raise ValueError("label_loss_func must be 'cross_entropy' or 'focal_loss', got %r" % (label_loss_func,))
+    params = label_loss_params
+    if params is None:
+        params = {}
+    elif isinstance(params, str):
+        params = ast.literal_eval(params)
+    if not isinstance(params, dict):
+        raise TypeError("label_loss_params must be a dict or its string form, got %r" % (label_loss_params,))
+    extra = sorted(k for k in params if k != "gamma")
+    if extra:
+        raise TypeError("label_focal_loss() got an unexpected keyword argument %r" % (extra[0],))
+    gamma = float(params.get("gamma", 2.0))
+    if not gamma >= 0.0:
+        raise ValueError("focal_loss: gamma must be >= 0, got %r" % (gamma,))
+    return gamma
+
+
+def focal_label_terms(logits, target_class, class_weight, gamma):
+    """w * nll * (1 - p_t)^gamma per query (label_focal_loss, glassrgbd.py:189-192) from logits (..., K) and target classes (...):
+    1 - p_t is the sum of the OTHER classes' probabilities, which does not cancel when p_t rounds to 1."""
+    hit = F.one_hot(target_class, logits.shape[-1]).bool()
+    nll = -F.log_softmax(logits, -1).gather(-1, target_class[..., None])[..., 0]
+    # a softmax of its own, not exp(log_softmax): behind a confidently wrong row (nll ~ 100) the backward of the shared log_softmax would
+    # subtract two gradients of size gamma * nll to leave one of size 1
+    u = F.softmax(logits, -1).masked_fill(hit, 0.0).sum(-1)
+    return class_weight[target_class] * nll * u ** gamma
+
+
 class _SetLossFn(torch.autograd.Function):
-    """Cost matrices of all decoder layers, device LSAP, weighted cross entropy and matched-pair L1 per layer - and their gradients -
-    as five launches (csrc/setloss.hip, csrc/lsap.hip); forward_packed's torch formulation (kept below as the A/B path) took ~65."""
+    """Cost matrices of all decoder layers, device LSAP, the label term (weighted cross entropy, or the focal loss when gamma is given)
+    and matched-pair L1 per layer - and their gradients - as five launches (csrc/setloss.hip, csrc/lsap.hip); forward_packed's torch
+    formulation (kept below as the A/B path) took ~65."""
 
     @staticmethod
-    def forward(ctx, logits, lines, tgt_lines, tgt_labels, meta, class_weight, num_items, world, w_line, w_class):
+    def forward(ctx, logits, lines, tgt_lines, tgt_labels, meta, class_weight, num_items, world, w_line, w_class, gamma=None):
         from . import hip
         lib = hip.library()
         L_, B, Q, K = logits.shape
@@ -92,9 +128,10 @@ class _SetLossFn(torch.autograd.Function):
         out = torch.empty((3, L_), dtype=torch.float32, device=dev)           # ce | l1 | sum of class weights
         bidx, valid = bidx.contiguous(), valid.contiguous()
         cw = class_weight.float().contiguous()
-        lib.set_losses_forward(logits, lines, tgt_lines, tgt_labels, bidx, valid, qot, cw, num_items, world, tc, out[0], out[1], out[2])
+        focal = {} if gamma is None else {"gamma": gamma}
+        lib.set_losses_forward(logits, lines, tgt_lines, tgt_labels, bidx, valid, qot, cw, num_items, world, tc, out[0], out[1], out[2], **focal)
         ctx.save_for_backward(logits, lines, tgt_lines, bidx, valid, qot, cw, num_items, tc, out)
-        ctx.world = world
+        ctx.world, ctx.focal = world, focal
         ctx.mark_non_differentiable(qot)
         return out[0], out[1], qot
 
@@ -106,17 +143,19 @@ class _SetLossFn(torch.autograd.Function):
         dlines = torch.zeros_like(lines)
         con = lambda g: None if g is None else g.contiguous().float()
         hip.library().set_losses_backward(logits, lines, tgt_lines, bidx, valid, qot, cw, num_items, ctx.world, tc, out[2], con(g_ce), con(g_l1),
-                                          dlogits, dlines)
-        return dlogits, dlines, None, None, None, None, None, None, None, None
+                                          dlogits, dlines, **ctx.focal)
+        return dlogits, dlines, None, None, None, None, None, None, None, None, None
 
 
 class SetCriterion(nn.Module):
     """SetCriterion with losses ['lines_labels', 'lines'] (+ aux), glassrgbd.py:133-358."""
 
-    def __init__(self, num_classes, weight_dict, eos_coef, losses, matcher):
+    def __init__(self, num_classes, weight_dict, eos_coef, losses, matcher, label_loss_func="cross_entropy", label_loss_params=None):
         super().__init__()
         self.num_classes, self.weight_dict, self.eos_coef, self.losses, self.matcher = \
             num_classes, weight_dict, eos_coef, losses, matcher
+        self.label_loss_func = label_loss_func
+        self.focal_gamma = focal_gamma(label_loss_func, label_loss_params)      # None: weighted cross entropy (:168), else :170
         w = torch.ones(num_classes + 1)
         w[-1] = eos_coef
         self.register_buffer("empty_weight", w)
@@ -135,7 +174,10 @@ class SetCriterion(nn.Module):
         bi, si = bi.to(dev), si.to(dev)
         tc = torch.full(out["pred_logits"].shape[:2], self.num_classes, dtype=torch.int64, device=dev)
         tc[bi, si] = torch.cat([t["labels"][j.to(dev)] for t, (_, j) in zip(targets, idx)])
-        ce = F.cross_entropy(out["pred_logits"].float().transpose(1, 2), tc, self.empty_weight)          # :168
+        if self.focal_gamma is None:
+            ce = F.cross_entropy(out["pred_logits"].float().transpose(1, 2), tc, self.empty_weight)      # :168
+        else:
+            ce = focal_label_terms(out["pred_logits"].float(), tc, self.empty_weight, self.focal_gamma).mean()   # :170, :193
         tl = torch.cat([t["lines"][j.to(dev)] for t, (_, j) in zip(targets, idx)], dim=0)
         l1 = F.l1_loss(out["pred_lines"].float()[bi, si], tl, reduction="none").sum() / num_items         # :239-242
         return {"loss_ce" + suffix: ce, "loss_line" + suffix: l1}
@@ -157,7 +199,8 @@ class SetCriterion(nn.Module):
         col_off, bidx, valid = meta[:B + 1], meta[B + 1:B + 1 + cap].long(), meta[B + 1 + cap:].float()
         if FUSED_SETLOSS:
             ce, l1, qi = _SetLossFn.apply(logits.contiguous(), lines.contiguous(), packed["lines"], packed["labels"], meta, self.empty_weight,
-                                          packed["num_items"], float(world), float(self.matcher.cost_line), float(self.matcher.cost_class))
+                                          packed["num_items"], float(world), float(self.matcher.cost_line), float(self.matcher.cost_class),
+                                          self.focal_gamma)
             self.last_query_of_target = qi.long()
             losses = {"loss_ce": ce[0], "loss_line": l1[0]}
             for i in range(L_ - 1):
@@ -182,9 +225,12 @@ class SetCriterion(nn.Module):
         tc = torch.full((L_, B, Q + 1), self.num_classes, dtype=torch.int64, device=logits.device)
         tc[li, bi, qi] = packed["labels"][None].expand(L_, -1)                         # padding columns land in the dummy slot Q
         tc = tc[:, :, :Q]
-        nll = F.cross_entropy(logits.reshape(L_ * B, Q, -1).transpose(1, 2), tc.reshape(L_ * B, Q), reduction="none")
-        w = self.empty_weight[tc.reshape(L_ * B, Q)]
-        ce = (nll * w).reshape(L_, -1).sum(1) / w.reshape(L_, -1).sum(1)                  # weighted mean per layer (:168)
+        if self.focal_gamma is None:
+            nll = F.cross_entropy(logits.reshape(L_ * B, Q, -1).transpose(1, 2), tc.reshape(L_ * B, Q), reduction="none")
+            w = self.empty_weight[tc.reshape(L_ * B, Q)]
+            ce = (nll * w).reshape(L_, -1).sum(1) / w.reshape(L_, -1).sum(1)              # weighted mean per layer (:168)
+        else:
+            ce = focal_label_terms(logits, tc, self.empty_weight, self.focal_gamma).reshape(L_, -1).mean(1)   # plain mean (:193)
         num_items = torch.clamp(packed["num_items"] / world, min=1.0)
         diff = (lines[li, bi, qi.clamp(max=Q - 1)] - packed["lines"][None]).abs().sum(-1)  # (L, cap)
         l1 = (diff * valid[None]).sum(1) / num_items                                       # (:239-242), padding masked out

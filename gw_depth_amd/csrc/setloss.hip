@@ -5,6 +5,8 @@
 //                            the rest "no object", weight eos_coef) and the L1 distance of the matched line pairs / num_items
 //                            (SetCriterion.loss_lines_labels / loss_lines_POST, /root/reference/src/models/glassrgbd.py:160-170,231-244)
 //   gwd_set_losses_backward  their gradients w.r.t. logits and lines.
+//   gwd_set_losses_focal_*   the same two launches with the label term of --label_loss_func focal_loss (SetCriterion.label_focal_loss,
+//                            /root/reference/src/models/glassrgbd.py:177-194): mean over the B*Q queries of w * nll * (1 - p_t)^gamma.
 // Targets arrive PADDED to a fixed capacity (criteria.PackedTargets): column t belongs to image bidx[t], valid[t] = 0 marks padding,
 // the LSAP hands padding columns the dummy query Q.  As torch ops this was ~40 launches forward and ~25 backward on a few KB of data.
 #include "common.h"
@@ -24,6 +26,18 @@ __device__ __forceinline__ void softmax_k(const float *lg, int K, float *p) {
     for (int k = 0; k < K; ++k) p[k] = p[k] / s;
 }
 
+// u = 1 - p[c] as the sum of the OTHER classes' probabilities (e_k = exp(lg[k] - mx), s = their sum over all k): 1 - p[c] cancels to 0 or
+// to one ulp of 1 once p[c] rounds to 1, the sum keeps the small tail that (1 - p_t)^gamma is made of
+__device__ __forceinline__ float others_prob(const float *lg, int K, int c, float mx, float s) {
+    float so = 0.f;
+    for (int k = 0; k < K; ++k)
+        if (k != c) so += expf(lg[k] - mx);
+    return so / s;
+}
+
+// u^g with torch.pow's conventions: u^0 = 1 also at u = 0
+__device__ __forceinline__ float focal_pow(float u, float g) { return g == 0.f ? 1.f : (g == 2.f ? u * u : powf(u, g)); }
+
 __global__ void match_cost_kernel(const float *__restrict__ logits, const float *__restrict__ lines, const float *__restrict__ tl,
                                   const int64_t *__restrict__ labels, float *__restrict__ cost, int64_t LBQ, int cap, int K, int D,
                                   float w_line, float w_class) {
@@ -41,14 +55,15 @@ __global__ void match_cost_kernel(const float *__restrict__ logits, const float 
     }
 }
 
-// one workgroup per decoder layer
+// one workgroup per decoder layer; FOCAL: ce[l] = sum(w * nll * u^gamma) / (B*Q) instead of the weighted mean sum(w * nll) / sum(w)
+template <bool FOCAL>
 __global__ __launch_bounds__(256) void set_losses_fwd_kernel(const float *__restrict__ logits, const float *__restrict__ lines,
                                                              const float *__restrict__ tl, const int64_t *__restrict__ labels,
                                                              const int32_t *__restrict__ bidx, const int32_t *__restrict__ valid,
                                                              const int32_t *__restrict__ qot, const float *__restrict__ cls_w,
                                                              const float *__restrict__ num_items, float world, int32_t *__restrict__ tc,
                                                              float *__restrict__ ce, float *__restrict__ l1, float *__restrict__ wsum,
-                                                             int B, int Q, int cap, int K, int D) {
+                                                             int B, int Q, int cap, int K, int D, float gamma) {
     __shared__ double red[3][256];
     const int l = blockIdx.x, tid = threadIdx.x, BQ = B * Q;
     int32_t *tcl = tc + (size_t)l * BQ;
@@ -76,7 +91,10 @@ __global__ __launch_bounds__(256) void set_losses_fwd_kernel(const float *__rest
         for (int k = 0; k < K; ++k) s += expf(lg[k] - mx);
         const int c = tcl[i];
         const float nll = -((lg[c] - mx) - logf(s)), w = cls_w[c];
-        s_n += (double)(nll * w);
+        if (FOCAL)
+            s_n += (double)(nll * w * focal_pow(others_prob(lg, K, c, mx, s), gamma));
+        else
+            s_n += (double)(nll * w);
         s_w += (double)w;
     }
     red[0][tid] = s_n;
@@ -93,13 +111,15 @@ __global__ __launch_bounds__(256) void set_losses_fwd_kernel(const float *__rest
     }
     if (tid == 0) {
         const float n = fmaxf(num_items[0] / world, 1.0f);
-        ce[l] = (float)(red[0][0] / red[1][0]);
+        ce[l] = (float)(red[0][0] / (FOCAL ? (double)BQ : red[1][0]));
         wsum[l] = (float)red[1][0];
         l1[l] = (float)(red[2][0] / (double)n);
     }
 }
 
-// dlogits fully written; dlines must be zero on entry (matched rows are added)
+// dlogits fully written; dlines must be zero on entry (matched rows are added).  FOCAL: d ce / d logits[k] =
+// w / (B*Q) * (p_k - [k = c]) * (u^gamma + gamma * u^(gamma-1) * p_t * nll), the second term absent for gamma = 0
+template <bool FOCAL>
 __global__ __launch_bounds__(256) void set_losses_bwd_kernel(const float *__restrict__ logits, const float *__restrict__ lines,
                                                              const float *__restrict__ tl, const int32_t *__restrict__ bidx,
                                                              const int32_t *__restrict__ valid, const int32_t *__restrict__ qot,
@@ -107,7 +127,7 @@ __global__ __launch_bounds__(256) void set_losses_bwd_kernel(const float *__rest
                                                              float world, const int32_t *__restrict__ tc, const float *__restrict__ wsum,
                                                              const float *__restrict__ g_ce, const float *__restrict__ g_l1,
                                                              float *__restrict__ dlogits, float *__restrict__ dlines, int B, int Q, int cap,
-                                                             int K, int D) {
+                                                             int K, int D, float gamma) {
     const int l = blockIdx.x, tid = threadIdx.x, BQ = B * Q;
     const float gce = g_ce ? g_ce[l] : 0.f, gl1 = g_l1 ? g_l1[l] : 0.f;
     const float ws = wsum[l];
@@ -116,7 +136,20 @@ __global__ __launch_bounds__(256) void set_losses_bwd_kernel(const float *__rest
         float p[KMAX];
         softmax_k(lg, K, p);
         const int c = tc[(size_t)l * BQ + i];
-        const float f = gce * cls_w[c] / ws;
+        float f;
+        if (FOCAL) {
+            float mx = lg[0];
+            for (int k = 1; k < K; ++k) mx = fmaxf(mx, lg[k]);
+            float s = 0.f;
+            for (int k = 0; k < K; ++k) s += expf(lg[k] - mx);
+            const float nll = -((lg[c] - mx) - logf(s)), u = others_prob(lg, K, c, mx, s);
+            float m = focal_pow(u, gamma);
+            // u = 0 means nll = 0: for gamma < 1 the limit of u^(gamma-1) * nll is 0, the product would be inf * 0
+            if (gamma != 0.f && (u > 0.f || gamma >= 1.f)) m += gamma * focal_pow(u, gamma - 1.f) * p[c] * nll;
+            f = gce * cls_w[c] / (float)BQ * m;
+        } else {
+            f = gce * cls_w[c] / ws;
+        }
         for (int k = 0; k < K; ++k) dlogits[((size_t)l * BQ + i) * K + k] = f * (p[k] - (k == c ? 1.f : 0.f));
     }
     const float n = fmaxf(num_items[0] / world, 1.0f);
@@ -148,18 +181,56 @@ extern "C" int gwd_match_cost(const float *logits, const float *lines, const flo
     return 0;
 }
 
+namespace {
+
+int launch_set_losses_fwd(bool focal, float gamma, const float *logits, const float *lines, const float *tgt_lines, const int64_t *tgt_labels,
+                          const int32_t *bidx, const int32_t *valid, const int32_t *qot, const float *class_weight, const float *num_items,
+                          float world, int32_t *target_class, float *ce, float *l1, float *wsum, int32_t L, int32_t B, int32_t Q, int32_t cap,
+                          int32_t K, int32_t D, void *stream) {
+    if (!logits || !lines || !tgt_lines || !tgt_labels || !bidx || !valid || !qot || !class_weight || !num_items || !target_class || !ce ||
+        !l1 || !wsum || L <= 0 || B <= 0 || Q <= 0 || cap <= 0)
+        return -1;
+    if (focal && !(gamma >= 0.f)) return -1;
+    if (K <= 0 || K > KMAX || D <= 0 || D > DMAX) return -4;
+    auto kern = focal ? set_losses_fwd_kernel<true> : set_losses_fwd_kernel<false>;
+    kern<<<L, 256, 0, (hipStream_t)stream>>>(logits, lines, tgt_lines, tgt_labels, bidx, valid, qot, class_weight, num_items, world, target_class,
+                                            ce, l1, wsum, B, Q, cap, K, D, gamma);
+    GWD_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_set_losses_bwd(bool focal, float gamma, const float *logits, const float *lines, const float *tgt_lines, const int32_t *bidx,
+                          const int32_t *valid, const int32_t *qot, const float *class_weight, const float *num_items, float world,
+                          const int32_t *target_class, const float *wsum, const float *g_ce, const float *g_l1, float *dlogits, float *dlines,
+                          int32_t L, int32_t B, int32_t Q, int32_t cap, int32_t K, int32_t D, void *stream) {
+    if (!logits || !lines || !tgt_lines || !bidx || !valid || !qot || !class_weight || !num_items || !target_class || !wsum || !dlogits ||
+        !dlines || L <= 0 || B <= 0 || Q <= 0 || cap <= 0)
+        return -1;
+    if (focal && !(gamma >= 0.f)) return -1;
+    if (K <= 0 || K > KMAX || D <= 0 || D > DMAX) return -4;
+    auto kern = focal ? set_losses_bwd_kernel<true> : set_losses_bwd_kernel<false>;
+    kern<<<L, 256, 0, (hipStream_t)stream>>>(logits, lines, tgt_lines, bidx, valid, qot, class_weight, num_items, world, target_class, wsum, g_ce,
+                                            g_l1, dlogits, dlines, B, Q, cap, K, D, gamma);
+    GWD_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
 extern "C" int gwd_set_losses_forward(const float *logits, const float *lines, const float *tgt_lines, const int64_t *tgt_labels,
                                       const int32_t *bidx, const int32_t *valid, const int32_t *qot, const float *class_weight,
                                       const float *num_items, float world, int32_t *target_class, float *ce, float *l1, float *wsum,
                                       int32_t L, int32_t B, int32_t Q, int32_t cap, int32_t K, int32_t D, void *stream) {
-    if (!logits || !lines || !tgt_lines || !tgt_labels || !bidx || !valid || !qot || !class_weight || !num_items || !target_class || !ce ||
-        !l1 || !wsum || L <= 0 || B <= 0 || Q <= 0 || cap <= 0)
-        return -1;
-    if (K <= 0 || K > KMAX || D <= 0 || D > DMAX) return -4;
-    set_losses_fwd_kernel<<<L, 256, 0, (hipStream_t)stream>>>(logits, lines, tgt_lines, tgt_labels, bidx, valid, qot, class_weight, num_items,
-                                                             world, target_class, ce, l1, wsum, B, Q, cap, K, D);
-    GWD_CHECK_LAUNCH();
-    return 0;
+    return launch_set_losses_fwd(false, 0.f, logits, lines, tgt_lines, tgt_labels, bidx, valid, qot, class_weight, num_items, world, target_class,
+                                 ce, l1, wsum, L, B, Q, cap, K, D, stream);
+}
+
+extern "C" int gwd_set_losses_focal_forward(const float *logits, const float *lines, const float *tgt_lines, const int64_t *tgt_labels,
+                                            const int32_t *bidx, const int32_t *valid, const int32_t *qot, const float *class_weight,
+                                            const float *num_items, float world, float gamma, int32_t *target_class, float *ce, float *l1,
+                                            float *wsum, int32_t L, int32_t B, int32_t Q, int32_t cap, int32_t K, int32_t D, void *stream) {
+    return launch_set_losses_fwd(true, gamma, logits, lines, tgt_lines, tgt_labels, bidx, valid, qot, class_weight, num_items, world, target_class,
+                                 ce, l1, wsum, L, B, Q, cap, K, D, stream);
 }
 
 extern "C" int gwd_set_losses_backward(const float *logits, const float *lines, const float *tgt_lines, const int32_t *bidx,
@@ -167,12 +238,15 @@ extern "C" int gwd_set_losses_backward(const float *logits, const float *lines, 
                                        float world, const int32_t *target_class, const float *wsum, const float *g_ce, const float *g_l1,
                                        float *dlogits, float *dlines, int32_t L, int32_t B, int32_t Q, int32_t cap, int32_t K, int32_t D,
                                        void *stream) {
-    if (!logits || !lines || !tgt_lines || !bidx || !valid || !qot || !class_weight || !num_items || !target_class || !wsum || !dlogits ||
-        !dlines || L <= 0 || B <= 0 || Q <= 0 || cap <= 0)
-        return -1;
-    if (K <= 0 || K > KMAX || D <= 0 || D > DMAX) return -4;
-    set_losses_bwd_kernel<<<L, 256, 0, (hipStream_t)stream>>>(logits, lines, tgt_lines, bidx, valid, qot, class_weight, num_items, world,
-                                                             target_class, wsum, g_ce, g_l1, dlogits, dlines, B, Q, cap, K, D);
-    GWD_CHECK_LAUNCH();
-    return 0;
+    return launch_set_losses_bwd(false, 0.f, logits, lines, tgt_lines, bidx, valid, qot, class_weight, num_items, world, target_class, wsum, g_ce,
+                                 g_l1, dlogits, dlines, L, B, Q, cap, K, D, stream);
+}
+
+extern "C" int gwd_set_losses_focal_backward(const float *logits, const float *lines, const float *tgt_lines, const int32_t *bidx,
+                                             const int32_t *valid, const int32_t *qot, const float *class_weight, const float *num_items,
+                                             float world, float gamma, const int32_t *target_class, const float *wsum, const float *g_ce,
+                                             const float *g_l1, float *dlogits, float *dlines, int32_t L, int32_t B, int32_t Q, int32_t cap,
+                                             int32_t K, int32_t D, void *stream) {
+    return launch_set_losses_bwd(true, gamma, logits, lines, tgt_lines, bidx, valid, qot, class_weight, num_items, world, target_class, wsum, g_ce,
+                                 g_l1, dlogits, dlines, L, B, Q, cap, K, D, stream);
 }

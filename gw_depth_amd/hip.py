@@ -33,7 +33,7 @@ ENTRY_POINTS = [
     "gwd_plane_loss_forward", "gwd_plane_loss_backward", "gwd_collate",
     "gwd_anchor_depth_forward", "gwd_anchor_depth_backward", "gwd_mha_flash_forward", "gwd_mha_flash_backward",
     "gwd_ref_scores_forward", "gwd_ref_scores_backward", "gwd_ref_mix_forward", "gwd_ref_mix_backward", "gwd_unpad_add_batch", "gwd_stem_pack", "gwd_stem_forward", "gwd_pos_sine", "gwd_silog_finalize", "gwd_psp_pool_forward", "gwd_psp_pool_backward",
-    "gwd_match_cost", "gwd_set_losses_forward", "gwd_set_losses_backward", "gwd_resample_u8_pass", "gwd_gather2d", "gwd_point_sample_backward_gather", "gwd_point_sample_framed_forward", "gwd_point_sample_framed_backward", "gwd_stride_place", "gwd_color_adjust", "gwd_bmm",
+    "gwd_match_cost", "gwd_set_losses_forward", "gwd_set_losses_backward", "gwd_set_losses_focal_forward", "gwd_set_losses_focal_backward", "gwd_resample_u8_pass", "gwd_gather2d", "gwd_point_sample_backward_gather", "gwd_point_sample_framed_forward", "gwd_point_sample_framed_backward", "gwd_stride_place", "gwd_color_adjust", "gwd_bmm",
     "gwd_dense_postprocess", "gwd_line_postprocess", "gwd_line_score",
     "gwd_resample_u8_pass_batch", "gwd_gather2d_batch", "gwd_color_adjust_batch",
 ]
@@ -214,6 +214,8 @@ class HipLibrary:
         L.gwd_match_cost.argtypes = [vp] * 5 + [i32] * 6 + [f32, f32, vp]
         L.gwd_set_losses_forward.argtypes = [vp] * 9 + [f32] + [vp] * 4 + [i32] * 6 + [vp]
         L.gwd_set_losses_backward.argtypes = [vp] * 8 + [f32] + [vp] * 6 + [i32] * 6 + [vp]
+        L.gwd_set_losses_focal_forward.argtypes = [vp] * 9 + [f32] * 2 + [vp] * 4 + [i32] * 6 + [vp]
+        L.gwd_set_losses_focal_backward.argtypes = [vp] * 8 + [f32] * 2 + [vp] * 6 + [i32] * 6 + [vp]
         L.gwd_color_adjust.argtypes = [vp, vp, vp, i64, i32, f32, vp]
         L.gwd_bmm.argtypes = [ctypes.POINTER(BmmDesc), vp]
         L.gwd_stride_place.argtypes = [vp, vp, vp] + [i32] * 8 + [vp]
@@ -907,23 +909,32 @@ class HipLibrary:
         self._check(self.lib.gwd_match_cost(_ptr(logits), _ptr(lines), _ptr(tgt_lines), _ptr(tgt_labels), _ptr(cost), L_, B, Q, cap, K, D,
                                             w_line, w_class, self._stream(logits, lines, cost)), "gwd_match_cost")
 
-    def set_losses_forward(self, logits, lines, tgt_lines, tgt_labels, bidx, valid, qot, class_weight, num_items, world, target_class, ce, l1, wsum):
+    def set_losses_forward(self, logits, lines, tgt_lines, tgt_labels, bidx, valid, qot, class_weight, num_items, world, target_class, ce, l1, wsum,
+                           gamma=None):
+        """gamma None: weighted cross entropy (gwd_set_losses_forward); a float: the focal label term (gwd_set_losses_focal_forward)."""
         L_, B, Q, K = logits.shape
         D, cap = lines.shape[-1], tgt_lines.shape[0]
         if any(t.dtype != torch.int32 for t in (bidx, valid, qot, target_class)) or tgt_labels.dtype != torch.int64:
             raise ValueError("set_losses_forward: int32 bidx / valid / qot / target_class and int64 labels expected")
-        self._check(self.lib.gwd_set_losses_forward(_ptr(logits), _ptr(lines), _ptr(tgt_lines), _ptr(tgt_labels), _ptr(bidx), _ptr(valid), _ptr(qot),
-                                                    _ptr(class_weight), _ptr(num_items), float(world), _ptr(target_class), _ptr(ce), _ptr(l1), _ptr(wsum),
-                                                    L_, B, Q, cap, K, D, self._stream(logits, lines, ce, l1)), "gwd_set_losses_forward")
+        head = (_ptr(logits), _ptr(lines), _ptr(tgt_lines), _ptr(tgt_labels), _ptr(bidx), _ptr(valid), _ptr(qot), _ptr(class_weight), _ptr(num_items),
+                float(world))
+        tail = (_ptr(target_class), _ptr(ce), _ptr(l1), _ptr(wsum), L_, B, Q, cap, K, D, self._stream(logits, lines, ce, l1))
+        if gamma is None:
+            self._check(self.lib.gwd_set_losses_forward(*head, *tail), "gwd_set_losses_forward")
+        else:
+            self._check(self.lib.gwd_set_losses_focal_forward(*head, float(gamma), *tail), "gwd_set_losses_focal_forward")
 
     def set_losses_backward(self, logits, lines, tgt_lines, bidx, valid, qot, class_weight, num_items, world, target_class, wsum, g_ce, g_l1,
-                            dlogits, dlines):
+                            dlogits, dlines, gamma=None):
         L_, B, Q, K = logits.shape
         D, cap = lines.shape[-1], tgt_lines.shape[0]
-        self._check(self.lib.gwd_set_losses_backward(_ptr(logits), _ptr(lines), _ptr(tgt_lines), _ptr(bidx), _ptr(valid), _ptr(qot), _ptr(class_weight),
-                                                     _ptr(num_items), float(world), _ptr(target_class), _ptr(wsum), _ptr(g_ce), _ptr(g_l1),
-                                                     _ptr(dlogits), _ptr(dlines), L_, B, Q, cap, K, D, self._stream(logits, lines, dlogits, dlines)),
-                    "gwd_set_losses_backward")
+        head = (_ptr(logits), _ptr(lines), _ptr(tgt_lines), _ptr(bidx), _ptr(valid), _ptr(qot), _ptr(class_weight), _ptr(num_items), float(world))
+        tail = (_ptr(target_class), _ptr(wsum), _ptr(g_ce), _ptr(g_l1), _ptr(dlogits), _ptr(dlines), L_, B, Q, cap, K, D,
+                self._stream(logits, lines, dlogits, dlines))
+        if gamma is None:
+            self._check(self.lib.gwd_set_losses_backward(*head, *tail), "gwd_set_losses_backward")
+        else:
+            self._check(self.lib.gwd_set_losses_focal_backward(*head, float(gamma), *tail), "gwd_set_losses_focal_backward")
 
     def lsap(self, cost, col_offsets, out, max_targets):
         """cost (layers,B,Q,sumT) fp32; col_offsets (B+1,) int32 DEVICE data (image b owns columns [off[b], off[b+1]),

@@ -361,7 +361,14 @@ int gwd_weight_prep_batch(const gwd_prep_job *jobs, int32_t n_jobs, int32_t tota
  *   gwd_set_losses_forward: per layer l: target_class (L,B,Q) int32 (the matched target's label at query qot[l][t], K-1 elsewhere),
  *     ce[l] = sum(nll * w) / sum(w) with w = class_weight[target class], wsum[l] = sum(w), l1[l] = sum over valid t of
  *     |lines[l, bidx[t], min(qot, Q-1)] - tgt_lines[t]|_1 / max(num_items[0] / world, 1)   (src/models/glassrgbd.py:160-170,231-244).
- *   gwd_set_losses_backward: dlogits (fully written) and dlines (ADDED to: caller zeroes) from g_ce[L] / g_l1[L] (either may be NULL). */
+ *   gwd_set_losses_backward: dlogits (fully written) and dlines (ADDED to: caller zeroes) from g_ce[L] / g_l1[L] (either may be NULL).
+ *   gwd_set_losses_focal_forward / _backward: the same operands plus gamma (>= 0, else -1), for --label_loss_func focal_loss
+ *     (SetCriterion.label_focal_loss, src/models/glassrgbd.py:177-194).  With c the target class of a query, p = softmax(logits),
+ *     p_t = p[c], nll = -log p_t, w = class_weight[c] and u = 1 - p_t taken as the SUM OF THE OTHER classes' probabilities (no
+ *     cancellation when p_t rounds to 1):  ce[l] = sum(w * nll * u^gamma) / (B*Q) - a plain mean over the queries, NOT the weighted
+ *     mean of the pair above (wsum is still written, and ignored by the backward);  d ce[l] / d logits[k] = g_ce[l] * w / (B*Q) *
+ *     (p_k - [k = c]) * (u^gamma + gamma * u^(gamma-1) * p_t * nll), with u^0 = 1 also at u = 0 and the second term absent for
+ *     gamma = 0.  target_class, l1 and dlines are those of the pair above.                                                         */
 int gwd_match_cost(const float *logits, const float *lines, const float *tgt_lines, const int64_t *tgt_labels, float *cost, int32_t L,
                    int32_t B, int32_t Q, int32_t cap, int32_t K, int32_t D, float w_line, float w_class, void *stream);
 int gwd_set_losses_forward(const float *logits, const float *lines, const float *tgt_lines, const int64_t *tgt_labels, const int32_t *bidx,
@@ -372,6 +379,14 @@ int gwd_set_losses_backward(const float *logits, const float *lines, const float
                             const int32_t *qot, const float *class_weight, const float *num_items, float world,
                             const int32_t *target_class, const float *wsum, const float *g_ce, const float *g_l1, float *dlogits,
                             float *dlines, int32_t L, int32_t B, int32_t Q, int32_t cap, int32_t K, int32_t D, void *stream);
+int gwd_set_losses_focal_forward(const float *logits, const float *lines, const float *tgt_lines, const int64_t *tgt_labels,
+                                 const int32_t *bidx, const int32_t *valid, const int32_t *qot, const float *class_weight,
+                                 const float *num_items, float world, float gamma, int32_t *target_class, float *ce, float *l1, float *wsum,
+                                 int32_t L, int32_t B, int32_t Q, int32_t cap, int32_t K, int32_t D, void *stream);
+int gwd_set_losses_focal_backward(const float *logits, const float *lines, const float *tgt_lines, const int32_t *bidx, const int32_t *valid,
+                                  const int32_t *qot, const float *class_weight, const float *num_items, float world, float gamma,
+                                  const int32_t *target_class, const float *wsum, const float *g_ce, const float *g_l1, float *dlogits,
+                                  float *dlines, int32_t L, int32_t B, int32_t Q, int32_t cap, int32_t K, int32_t D, void *stream);
 
 /* Padding mask of one feature level + sine position embeddings from it (src/models/backbone.py:81-88: F.interpolate(nearest) of the
  * batch mask; src/models/position_encoding.py:28-48: PositionEmbeddingSine).  Two stages, either may be skipped:
