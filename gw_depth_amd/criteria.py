@@ -233,7 +233,8 @@ class SetCriterion(nn.Module):
             ce = focal_label_terms(logits, tc, self.empty_weight, self.focal_gamma).reshape(L_, -1).mean(1)   # plain mean (:193)
         num_items = torch.clamp(packed["num_items"] / world, min=1.0)
         diff = (lines[li, bi, qi.clamp(max=Q - 1)] - packed["lines"][None]).abs().sum(-1)  # (L, cap)
-        l1 = (diff * valid[None]).sum(1) / num_items                                       # (:239-242), padding masked out
+        # (:239-242), padding masked out - and the surplus targets of an image with more targets than queries, which sit on Q too
+        l1 = (diff * valid[None] * (qi < Q)).sum(1) / num_items
         losses = {"loss_ce": ce[0], "loss_line": l1[0]}
         for i in range(L_ - 1):
             losses[f"loss_ce_{i}"] = ce[i + 1]

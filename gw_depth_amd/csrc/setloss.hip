@@ -8,7 +8,8 @@
 //   gwd_set_losses_focal_*   the same two launches with the label term of --label_loss_func focal_loss (SetCriterion.label_focal_loss,
 //                            /root/reference/src/models/glassrgbd.py:177-194): mean over the B*Q queries of w * nll * (1 - p_t)^gamma.
 // Targets arrive PADDED to a fixed capacity (criteria.PackedTargets): column t belongs to image bidx[t], valid[t] = 0 marks padding,
-// the LSAP hands padding columns the dummy query Q.  As torch ops this was ~40 launches forward and ~25 backward on a few KB of data.
+// the LSAP hands padding columns the dummy query Q
+// (and, where an image has more targets than queries, its unmatched targets: they take no part in either term).  As torch ops this was ~40 launches forward and ~25 backward on a few KB of data.
 #include "common.h"
 
 namespace {
@@ -72,10 +73,11 @@ __global__ __launch_bounds__(256) void set_losses_fwd_kernel(const float *__rest
     double s_l1 = 0.0;
     for (int t = tid; t < cap; t += 256) {
         const int q = qot[(size_t)l * cap + t], b = bidx[t];
-        if (q < Q && valid[t]) tcl[b * Q + q] = (int32_t)labels[t];             // padding columns sit on the dummy query Q
-        if (valid[t]) {
-            const int qc = q < Q ? q : Q - 1;
-            const float *pl = lines + ((size_t)l * BQ + (size_t)b * Q + qc) * D;
+        // padding columns sit on the dummy query Q, and so do the surplus targets of an image with more targets than queries: neither
+        // carries a label or an L1 term
+        if (q >= 0 && q < Q && valid[t]) {
+            tcl[b * Q + q] = (int32_t)labels[t];
+            const float *pl = lines + ((size_t)l * BQ + (size_t)b * Q + q) * D;
             float a = 0.f;
             for (int d = 0; d < D; ++d) a += fabsf(pl[d] - tl[(size_t)t * D + d]);
             s_l1 += (double)a;
@@ -156,8 +158,8 @@ __global__ __launch_bounds__(256) void set_losses_bwd_kernel(const float *__rest
     for (int t = tid; t < cap; t += 256) {
         if (!valid[t]) continue;
         const int q = qot[(size_t)l * cap + t], b = bidx[t];
-        const int qc = q < Q ? q : Q - 1;
-        const size_t row = ((size_t)l * BQ + (size_t)b * Q + qc) * D;
+        if (q < 0 || q >= Q) continue;                                          // a surplus target (more targets than queries): no pair
+        const size_t row = ((size_t)l * BQ + (size_t)b * Q + q) * D;
         for (int d = 0; d < D; ++d) {
             const float df = lines[row + d] - tl[(size_t)t * D + d];
             const float sg = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);

@@ -14,11 +14,34 @@ from . import hip
 MEAN, STD = (0.538, 0.494, 0.453), (0.257, 0.263, 0.273)          # src/datasets/coco.py:78
 
 
-def device_collate(samples, device="cuda", dtype=torch.float32, mean=MEAN, std=STD):
+def bucket_shape(h, w, step=64):
+    """(H, W): h and w rounded up to a multiple of `step`.  Augmented training batches come in hundreds of padded sizes (DESIGN.md
+    §13); collated to a bucket they come in a dozen, and TrainStep(graph=True) keeps one captured step per size."""
+    step = int(step)
+    if step < 1:
+        raise ValueError("bucket_shape: step must be >= 1, got %r" % (step,))
+    return -(-int(h) // step) * step, -(-int(w) // step) * step
+
+
+def padded_size(h, w, pad_to):
+    """Output size of a batch whose largest item is (h, w): pad_to None = (h, w), an int = bucket_shape with that step, an (H, W) pair =
+    that size (ValueError if an item does not fit)."""
+    if pad_to is None:
+        return int(h), int(w)
+    if isinstance(pad_to, (tuple, list)):
+        H, W = (int(x) for x in pad_to)
+        if H < h or W < w:
+            raise ValueError("pad_to=%r is smaller than an item of the batch (%d, %d)" % (tuple(pad_to), h, w))
+        return H, W
+    return bucket_shape(h, w, pad_to)
+
+
+def device_collate(samples, device="cuda", dtype=torch.float32, mean=MEAN, std=STD, pad_to=None):
     """samples: list (<= 16) of (rgb uint8 (h,w,3), depth_mm integer (h,w), labels uint8 (h,w)) host or device tensors, as
     decoded (any element but rgb may be None for the whole batch).  Returns the batch dict TrainStep / evaluate take:
     images (B,3,H,W) [a view of the pixel-major buffer the model reads in place], pad_mask (B,H,W) bool, depth (B,1,H,W) fp32
-    metres, seg (B,1,H,W) int64."""
+    metres, seg (B,1,H,W) int64.  (H, W) is the batch maximum, or padded_size() of it under `pad_to`: more of the same padding
+    (image 0, mask True, depth 0, label 0) that an image batched with a larger one gets."""
     lib = hip.library()
     if not 0 < len(samples) <= hip.COLLATE_BATCH:
         raise ValueError("1..%d images per call" % hip.COLLATE_BATCH)
@@ -37,7 +60,7 @@ def device_collate(samples, device="cuda", dtype=torch.float32, mean=MEAN, std=S
         if r.dim() != 3 or r.shape[2] != 3 or (d is not None and d.shape != r.shape[:2]) or (l is not None and l.shape != r.shape[:2]):
             raise ValueError("rgb must be (h,w,3) with depth / labels of the same (h,w)")
     B = len(dev_samples)
-    H, W = max(s[0].shape[0] for s in dev_samples), max(s[0].shape[1] for s in dev_samples)
+    H, W = padded_size(max(s[0].shape[0] for s in dev_samples), max(s[0].shape[1] for s in dev_samples), pad_to)
     have_d, have_l = dev_samples[0][1] is not None, dev_samples[0][2] is not None
     images = torch.empty((B, H, W, 3), dtype=dtype, device=dev)
     mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
@@ -378,11 +401,11 @@ def assemble_item(rgb, depth_mm, labels, shapes, image_id, with_center=True, par
     return rgb, depth_mm, labels, _item_target(lines, ids, centres, image_id, h, w, fh, fw, with_center)
 
 
-def assemble_batch(items, params, device="cuda", dtype=torch.float32, with_center=True):
+def assemble_batch(items, params, device="cuda", dtype=torch.float32, with_center=True, pad_to=None):
     """A whole batch from DECODED arrays: assemble_item for every item and device_collate, with the transform chains of all
     items in DeviceAugment.apply_batch's fixed number of launches.  items: list (<= 16) of (rgb, depth_mm, labels, shapes,
     image_id) as assemble_item takes them; params: one DeviceAugment.params dict (or None = no step) per item.
-    Returns (the batch dict of device_collate, the list of target dicts)."""
+    pad_to: device_collate's.  Returns (the batch dict of device_collate, the list of target dicts)."""
     if len(items) != len(params):
         raise ValueError("one params entry per item")
     sizes = [(int(it[0].shape[0]), int(it[0].shape[1])) for it in items]
@@ -391,7 +414,7 @@ def assemble_batch(items, params, device="cuda", dtype=torch.float32, with_cente
                                     poly_ids=[t[1] for t in tg], centres=[t[2] for t in tg])
     targets = [_item_target(o[3], o[4], o[5], it[4], h, w, int(o[0].shape[0]), int(o[0].shape[1]), with_center)
                for o, it, (h, w) in zip(out, items, sizes)]
-    return device_collate([o[:3] for o in out], device=device, dtype=dtype), targets
+    return device_collate([o[:3] for o in out], device=device, dtype=dtype, pad_to=pad_to), targets
 
 
 class DeviceAugment:

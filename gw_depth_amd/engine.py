@@ -47,13 +47,68 @@ def never_used(name):
 MAX_GRAPHS = 6          # captured batch signatures kept (least recently used goes first); all share one memory pool
 
 
+class GraphCache:
+    """Which batch signatures of a graph-mode TrainStep hold a captured step: pure bookkeeping, no device.
+
+    `entries` is the least-recently-used ordered table of the signatures that have been through a capture attempt (captured, or
+    refused: {"graph": None, ...}); `seen` counts the sights of the signatures still waiting.  A signature is captured at its `capture_after`-th
+    sight and runs eagerly before that, so a shape that shows up once in an epoch never pays the warm-up passes of a capture.  The
+    bound is `max_graphs`, or the module's MAX_GRAPHS read at every call when it is None."""
+    COUNTERS = ("replays", "captures", "eager_steps", "evictions", "refused", "host_matcher_steps")
+    SEEN_MAX = 4096         # waiting signatures remembered
+
+    def __init__(self, max_graphs=None, capture_after=1):
+        if max_graphs is not None and int(max_graphs) < 1:
+            raise ValueError("max_graphs must be >= 1, got %r" % (max_graphs,))
+        if int(capture_after) < 1:
+            raise ValueError("capture_after must be >= 1, got %r" % (capture_after,))
+        self.max_graphs = None if max_graphs is None else int(max_graphs)
+        self.capture_after = int(capture_after)
+        self.entries = OrderedDict()
+        self.seen = {}
+        self.stats = dict.fromkeys(self.COUNTERS, 0)
+
+    def bound(self):
+        return MAX_GRAPHS if self.max_graphs is None else self.max_graphs
+
+    def lookup(self, key):
+        """One sight of `key` -> ("known", entry): it has been through a capture attempt (entry["graph"] is None if that was refused)
+        and is the most recently used now; ("wait", None): run it eagerly; ("capture", None): capture it now and store() the entry."""
+        ent = self.entries.get(key)
+        if ent is not None:
+            self.entries.move_to_end(key)
+            return "known", ent
+        n = self.seen.pop(key, 0) + 1                  # re-inserted at the young end
+        if n >= self.capture_after:
+            return "capture", None                     # its count is dropped: an evicted signature starts over
+        self.seen[key] = n
+        while len(self.seen) > self.SEEN_MAX:          # waiting signatures are bounded too: the one not seen for longest goes
+            del self.seen[next(iter(self.seen))]
+        return "wait", None
+
+    def make_room(self):
+        """Drop least recently used entries until one more fits; called BEFORE a capture, so the executables go first."""
+        while len(self.entries) >= max(self.bound(), 1):
+            self.entries.popitem(last=False)
+            self.stats["evictions"] += 1
+
+    def store(self, key, ent):
+        self.make_room()
+        self.entries[key] = ent
+        self.stats["captures" if ent.get("graph") is not None else "refused"] += 1
+        return ent
+
+    def count(self, name, n=1):
+        self.stats[name] += n
+
+
 def _align(n):
     return (n + ALIGN - 1) // ALIGN * ALIGN
 
 
 class TrainStep:
     def __init__(self, model, criterions, cfg, compute_dtype=torch.float32, bucket_mb=32.0, process_group=None,
-                 check_finite=True, data_parallel=True, graph=False, segments=None):
+                 check_finite=True, data_parallel=True, graph=False, segments=None, max_graphs=None, capture_after=1):
         self.model, self.cfg = model, cfg
         self.criterion, self.criterion_depth, self.criterion_seg, self.criterion_plane = criterions
         self.compute_dtype = compute_dtype
@@ -62,7 +117,8 @@ class TrainStep:
         self.device_matcher = True        # gwd_lsap + sync-free criterion (taps / teacher-forced tests use the host matcher)
         self._packs = {}                  # (batch size, capacity) -> PackedTargets of the eager path
         self.use_graph = bool(graph)      # capture zero_grad+forward+losses+backward of a batch signature as a chain of HIP graphs
-        self._graphs = OrderedDict()
+        self._cache = GraphCache(max_graphs, capture_after)     # which signatures are captured, and the counters of graph_stats()
+        self._graphs = self._cache.entries                      # signature -> {"graph": chain or None, ...}, least recently used first
         self._pool = None
         self._gstream = None
         self._pending_checks = []
@@ -235,12 +291,24 @@ class TrainStep:
             w.wait()
         self._works = []
 
+    def _device_matchable(self, sizes):
+        """gwd_lsap's limits: at most hip.LSAP_MAX_TARGETS queries, and as many targets in one image (a batch without any target
+        is fine: every column of its table is padding)."""
+        q = int(self.model.num_queries)                # no silent default: a model that hides its query count is an error here
+        return q <= hip.LSAP_MAX_TARGETS and max(sizes, default=0) <= hip.LSAP_MAX_TARGETS
+
+    def graph_stats(self):
+        """Counters since construction: replays (steps run as a captured chain), captures, eager_steps (graph-mode steps that ran
+        eagerly: a signature still waiting for its capture_after-th sight, a refused capture, taps, the host matcher), evictions,
+        refused (captures refused or failed) and host_matcher_steps (steps, in any mode, matched by scipy on the host)."""
+        return dict(self._cache.stats)
+
     def _packed(self, targets, store=None):
         """Static-shape device form of the targets for the sync-free criterion (criteria.PackedTargets, one per capacity
-        class); None when the device LSAP cannot take the batch (no targets at all, or more than 64 in one image): the
+        class); None when the device LSAP cannot take the batch (more than 1024 queries, or targets in one image): the
         caller then uses the host matcher."""
         sizes = [int(len(t["labels"])) for t in targets]
-        if sum(sizes) == 0 or max(sizes) > hip.LSAP_MAX_TARGETS:
+        if not self._device_matchable(sizes):
             return None
         store = self._packs if store is None else store
         key = (len(sizes), target_capacity(sum(sizes)))
@@ -332,6 +400,8 @@ class TrainStep:
         """Forward, losses, backward and (N > 1) the bucketed gradient all-reduce; leaves SUMMED grads in flat_g."""
         self.model.train()
         packed = self._packed(batch["targets"]) if self.device_matcher else None
+        if packed is None:
+            self._cache.count("host_matcher_steps")
         match = (self.criterion.matcher, batch["targets"]) if (packed is None and hasattr(self.criterion.matcher, "prefetch")) else None
         weights = self.weights if (self.compute_dtype == torch.bfloat16 and batch["images"].is_cuda) else None
         if weights is not None:
@@ -446,15 +516,14 @@ class TrainStep:
 
     def _graph_entry(self, batch):
         sizes = [int(len(t["labels"])) for t in batch["targets"]]
-        if sum(sizes) == 0 or max(sizes) > hip.LSAP_MAX_TARGETS:
+        if not self._device_matchable(sizes):
             return None                                # device LSAP limits: this batch runs eagerly with the host matcher
         key = (tuple(batch["images"].shape), target_capacity(sum(sizes)))
-        ent = self._graphs.get(key)
-        if ent is not None:
-            self._graphs.move_to_end(key)
-            return ent
-        while len(self._graphs) >= MAX_GRAPHS:          # bounded cache; the executables go, the shared pool keeps the memory
-            self._graphs.popitem(last=False)
+        cache = self._cache
+        verdict, ent = cache.lookup(key)
+        if verdict != "capture":
+            return ent                                 # a hit, or None: the signature runs eagerly until its capture_after-th sight
+        cache.make_room()                              # bounded cache; the executables go, the shared pool keeps the memory
         dev = self.flat_p.device
         st = {k: batch[k].clone() for k in ("images", "pad_mask", "depth", "seg")}
         st["packed"] = PackedTargets(len(sizes), key[1], dev).update(batch["targets"])
@@ -478,20 +547,17 @@ class TrainStep:
                           "memset nodes do not replay correctly in HIP graphs on this ROCm" % memsets)
             if reason is not None:
                 warnings.warn("gw_depth_amd: HIP-graph capture refused for batch signature %r, running eager: %s" % (key, reason))
-                ent = self._graphs[key] = {"graph": None, "reason": reason}
-                return ent
+                return cache.store(key, {"graph": None, "reason": reason})
             try:
                 chain, res = self._capture(st)
             except RuntimeError as e:                   # capture invalidated: keep training, eagerly, and say so
                 torch.cuda.synchronize()
                 self._state = None
                 warnings.warn("gw_depth_amd: HIP-graph capture failed for batch signature %r, running eager: %s" % (key, e))
-                ent = self._graphs[key] = {"graph": None, "reason": str(e)}
-                return ent
+                return cache.store(key, {"graph": None, "reason": str(e)})
         finally:
             self._launch = launch
-        ent = self._graphs[key] = {"graph": chain, "static": st, "result": res}
-        return ent
+        return cache.store(key, {"graph": chain, "static": st, "result": res})
 
     def _on_graph_stream(self, batch, taps):
         """Eager forward/backward of a graph-mode TrainStep: same stream as the captures (see _graph_stream), and the same
@@ -506,7 +572,9 @@ class TrainStep:
     def _graph_step(self, batch):
         ent = self._graph_entry(batch)
         if ent is None or ent["graph"] is None:
+            self._cache.count("eager_steps")
             return self._on_graph_stream(batch, None)
+        self._cache.count("replays")
         st = ent["static"]
         for k in ("images", "pad_mask", "depth", "seg"):
             st[k].copy_(batch[k], non_blocking=True)
@@ -524,6 +592,8 @@ class TrainStep:
     def __call__(self, batch, taps=None):
         """batch: dict(images (B,3,H,W), pad_mask (B,H,W) bool, depth (B,1,H,W), seg (B,1,H,W) i64, targets)."""
         if self.use_graph and batch["images"].is_cuda:
+            if taps is not None:
+                self._cache.count("eager_steps")
             out, total, terms = self._graph_step(batch) if taps is None else self._on_graph_stream(batch, taps)
         else:
             out, total, terms = self.forward_backward(batch, taps)

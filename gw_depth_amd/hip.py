@@ -91,7 +91,7 @@ class ColsumJob(ctypes.Structure):
 
 
 COLSUM_BATCH = 16
-LSAP_MAX_TARGETS = 64     # gwd_lsap: targets per image (MAXT in csrc/lsap.hip)
+LSAP_MAX_TARGETS = 1024   # gwd_lsap: targets per image and queries (MAXN in csrc/lsap.hip)
 COLLATE_BATCH = 16
 
 
@@ -938,8 +938,8 @@ class HipLibrary:
 
     def lsap(self, cost, col_offsets, out, max_targets):
         """cost (layers,B,Q,sumT) fp32; col_offsets (B+1,) int32 DEVICE data (image b owns columns [off[b], off[b+1]),
-        at most max_targets <= 64 of them; columns from off[B] on are padding); out (layers,sumT) int32: the query
-        assigned to every target column, Q for padding columns."""
+        at most max_targets <= 1024 of them; columns from off[B] on are padding); out (layers,sumT) int32: the query
+        assigned to every target column, Q for padding columns and for the surplus targets of an image with more than Q."""
         L_, B, Q, sumT = cost.shape
         self._check(self.lib.gwd_lsap(_ptr(cost), _ptr(col_offsets), _ptr(out), L_, B, Q, sumT, max_targets,
                                       self._stream(cost, col_offsets, out)), "gwd_lsap")

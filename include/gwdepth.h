@@ -305,10 +305,13 @@ int gwd_certain_sample(const float *pred_small, const float *pred_large, float *
 /* Linear sum assignment of the line matcher on the device (replaces scipy.optimize.linear_sum_assignment at
  * src/models/matcher.py:74 and its 6 host syncs per step).  cost [layers][B][Q][sum_targets] fp32 is the block
  * cost matrix of matcher.py:52-70; image b owns columns col_offsets[b] .. col_offsets[b+1]-1 (int32 [B+1]).
- * query_of_target [layers][sum_targets] int32 receives the query matched to every target (targets <= Q, <= 64).
+ * query_of_target [layers][sum_targets] int32 receives the query matched to every target (Q <= 1024, targets of one
+ * image <= 1024, else -4).  An image with MORE targets than queries has every query matched, as scipy does on the
+ * Q x T matrix; its surplus targets receive the dummy query index Q.
  * The offsets are DEVICE data: sum_targets may be a fixed capacity larger than col_offsets[B]; the padding columns
  * col_offsets[B] .. sum_targets-1 are never read and receive the dummy query index Q, so one captured launch serves
- * batches with any per-image target counts (max_targets is the host's bound on them, <= 64).                    */
+ * batches with any per-image target counts (max_targets is the host's bound on them, <= 1024).
+ * A non-finite cost is read as a large finite one; the kernel's running time is bounded by Q and the counts alone. */
 int gwd_lsap(const float *cost, const int32_t *col_offsets, int32_t *query_of_target, int32_t layers, int32_t B,
              int32_t Q, int32_t sum_targets, int32_t max_targets, void *stream);
 
@@ -360,7 +363,8 @@ int gwd_weight_prep_batch(const gwd_prep_job *jobs, int32_t n_jobs, int32_t tota
  *     (cap, int64)]  (HungarianMatcher_Line.forward, src/models/matcher.py:52-70).
  *   gwd_set_losses_forward: per layer l: target_class (L,B,Q) int32 (the matched target's label at query qot[l][t], K-1 elsewhere),
  *     ce[l] = sum(nll * w) / sum(w) with w = class_weight[target class], wsum[l] = sum(w), l1[l] = sum over valid t of
- *     |lines[l, bidx[t], min(qot, Q-1)] - tgt_lines[t]|_1 / max(num_items[0] / world, 1)   (src/models/glassrgbd.py:160-170,231-244).
+ *     |lines[l, bidx[t], qot] - tgt_lines[t]|_1 / max(num_items[0] / world, 1)   (src/models/glassrgbd.py:160-170,231-244); a valid t
+ *     with qot = Q (a surplus target of an image with more targets than queries) has no label and no L1 term, forward and backward.
  *   gwd_set_losses_backward: dlogits (fully written) and dlines (ADDED to: caller zeroes) from g_ce[L] / g_l1[L] (either may be NULL).
  *   gwd_set_losses_focal_forward / _backward: the same operands plus gamma (>= 0, else -1), for --label_loss_func focal_loss
  *     (SetCriterion.label_focal_loss, src/models/glassrgbd.py:177-194).  With c the target class of a query, p = softmax(logits),
