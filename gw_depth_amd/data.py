@@ -505,7 +505,7 @@ class DeviceAugment:
         return rgb, depth_mm, labels, lines, keep
 
     @staticmethod
-    def apply_batch(frames, lines, params, poly_ids=None, centres=None):
+    def apply_batch(frames, lines, params, poly_ids=None, centres=None, carry=None):
         """apply() for a whole batch in a number of launches that does not depend on its size.  frames: list of 1..16
         (rgb, depth_mm | None, labels | None) device tensors of any sizes, lines / params (and poly_ids / centres, when given):
         lists of the same length.  Returns the list of the tuples apply() returns, value for value.
@@ -514,7 +514,10 @@ class DeviceAugment:
         int32 buffer, uploaded with one asynchronous copy - and then launched: at most four grouped resample launches (first and
         second BILINEAR resize, horizontal and vertical), one grouped gather (depth, labels and the RGB frames that are flipped /
         cropped / copied but never resized), and per jitter slot one grouped adjustment in place plus one luma-sum launch where a
-        frame's adjustment is a contrast.  A chain may hold at most two size-changing resizes (the reference's chains hold two)."""
+        frame's adjustment is a contrast.  A chain may hold at most two size-changing resizes (the reference's chains hold two).
+
+        carry: an int32 array that rides along in the table buffer's one upload (per-frame sizes a later kernel reads on the
+        device, say); the call then returns (the list, the device copy of `carry` in its shape)."""
         n = len(frames)
         if not 0 < n <= hip.AUGMENT_BATCH:
             raise ValueError("1..%d frames per call" % hip.AUGMENT_BATCH)
@@ -522,13 +525,18 @@ class DeviceAugment:
             raise ValueError("one lines / params (/ poly_ids / centres) entry per frame")
         lib = hip.library()
         plan = _BatchPlan(frames[0][0].device)
+        if carry is not None:
+            carry = np.ascontiguousarray(carry, dtype=np.int32)
+            carry_off = plan.table(carry)
         out = []
         for f, ((rgb, depth_mm, labels), p) in enumerate(zip(frames, params)):
             images = plan.add_frame(rgb, depth_mm, labels, p)
             targets = _transform_targets(int(rgb.shape[0]), int(rgb.shape[1]), lines[f], p, None if poly_ids is None else poly_ids[f],
                                          None if centres is None else centres[f])
             out.append(images + targets)
-        plan.launch(lib)
+        tables = plan.launch(lib)
+        if carry is not None:
+            return out, tables[carry_off:carry_off + carry.size].view(carry.shape)
         return out
 
 
@@ -761,3 +769,4 @@ class _BatchPlan:
             if contrast:                              # the frames' luma sums, from the images as they stand before the blend
                 lib.color_adjust_batch(slot, sums[s], sums_only=True)
             lib.color_adjust_batch(slot, sums[s] if contrast else None)
+        return tables

@@ -35,6 +35,7 @@ ENTRY_POINTS = [
     "gwd_ref_scores_forward", "gwd_ref_scores_backward", "gwd_ref_mix_forward", "gwd_ref_mix_backward", "gwd_unpad_add_batch", "gwd_stem_pack", "gwd_stem_forward", "gwd_pos_sine", "gwd_silog_finalize", "gwd_psp_pool_forward", "gwd_psp_pool_backward",
     "gwd_match_cost", "gwd_set_losses_forward", "gwd_set_losses_backward", "gwd_set_losses_focal_forward", "gwd_set_losses_focal_backward", "gwd_resample_u8_pass", "gwd_gather2d", "gwd_point_sample_backward_gather", "gwd_point_sample_framed_forward", "gwd_point_sample_framed_backward", "gwd_stride_place", "gwd_color_adjust", "gwd_bmm",
     "gwd_dense_postprocess", "gwd_line_postprocess", "gwd_line_score",
+    "gwd_dense_postprocess_resized",
     "gwd_resample_u8_pass_batch", "gwd_gather2d_batch", "gwd_color_adjust_batch",
 ]
 
@@ -255,6 +256,7 @@ class HipLibrary:
         L.gwd_query_workspace.restype = ctypes.c_int64
         L.gwd_eval_accumulate.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, i64, f32, f32, i32, i32, vp]
         L.gwd_dense_postprocess.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp]
+        L.gwd_dense_postprocess_resized.argtypes = [vp, vp, i64, i64, i64, vp, vp, i32, vp, vp, vp] + [i32] * 5 + [f32, f32, i32, i32, vp]
         L.gwd_line_postprocess.argtypes = [vp] * 7 + [i32, i32, i32, f32, vp]
         dp = ctypes.POINTER(ctypes.c_double)
         L.gwd_line_score.argtypes = [vp] * 5 + [dp, i32, dp, i32] + [vp] * 4 + [i32] * 4 + [i64, i64, vp]
@@ -502,6 +504,26 @@ class HipLibrary:
             _ptr(depth), ctypes.c_void_p(seg.data_ptr()), sb, sp, sc, _ptr(sizes), _ptr(depth_out), _ptr(depth_mm), _ptr(label),
             B, H, W, float(dmin), float(dmax), dtype_code(depth), dtype_code(seg),
             self._stream(depth, seg, sizes, depth_out, depth_mm, label)), "gwd_dense_postprocess")
+
+    def dense_postprocess_resized(self, depth, seg, seg_strides, sizes, frame_sizes, twin, depth_out, depth_mm, label, B, H, W, Fh, Fw,
+                                  dmin, dmax):
+        """gwd_dense_postprocess_resized.  depth / seg hold B + twin images of (H, W); sizes (B,2) int32 or None, frame_sizes (B,2)
+        int32, both on the device; the outputs are (B, Fh, Fw)."""
+        for t, dt in ((sizes, torch.int32), (frame_sizes, torch.int32), (depth_out, torch.float32), (depth_mm, torch.uint16),
+                      (label, torch.uint8)):
+            if t is not None and t.dtype != dt:
+                raise TypeError("gwd_dense_postprocess_resized: expected %s, got %s" % (dt, t.dtype))
+        n = B * Fh * Fw
+        if twin < 0 or depth.numel() != (B + twin) * H * W or depth_out.numel() != n or label.numel() != n \
+                or (depth_mm is not None and depth_mm.numel() != n) or (sizes is not None and sizes.numel() != 2 * B) \
+                or frame_sizes.numel() != 2 * B:
+            raise ValueError("gwd_dense_postprocess_resized: operand sizes do not match (B, twin, H, W, Fh, Fw) = (%d, %d, %d, %d, %d, %d)"
+                             % (B, twin, H, W, Fh, Fw))
+        sb, sp, sc = (int(v) for v in seg_strides)
+        self._check(self.lib.gwd_dense_postprocess_resized(
+            _ptr(depth), ctypes.c_void_p(seg.data_ptr()), sb, sp, sc, _ptr(sizes), _ptr(frame_sizes), int(twin), _ptr(depth_out),
+            _ptr(depth_mm), _ptr(label), B, H, W, Fh, Fw, float(dmin), float(dmax), dtype_code(depth), dtype_code(seg),
+            self._stream(depth, seg, sizes, frame_sizes, depth_out, depth_mm, label)), "gwd_dense_postprocess_resized")
 
     def line_postprocess(self, logits, lines, sizes, scores, lines_px, order, count, B, Q, ld, thresh):
         """gwd_line_postprocess: logits (B,Q,2) / lines (B,Q,ld) fp32, sizes (B,2) int32; Q <= 1024."""

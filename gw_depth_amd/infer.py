@@ -15,9 +15,10 @@ import gc
 import warnings
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
-from . import engine, ops
+from . import data, engine, hip, ops
 from .model import NestedTensor, nested_tensor_from_tensor_list
 
 RESULT_KEYS = ("depth", "depth_mm", "labels", "scores", "lines", "order", "count", "sizes")
@@ -58,6 +59,9 @@ class InferenceSession:
     by address) stay valid.  The cache is keyed by address: parameter storage must not move after the session is built -
     TrainStep.__init__ moves every parameter into its flat buffer, so build the session AFTER the TrainStep; refresh() checks
     and raises.  compute_dtype=torch.float32 has no copies to freeze (the kernels read the parameters themselves).
+
+    sess.predict_frames(frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False): decoded uint8 (h,w,3) camera
+    frames in, the same results at every frame's OWN size out (see the method).
 
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
@@ -271,4 +275,63 @@ class InferenceSession:
         res = self._run(samples, target_sizes, True)[1]
         if copy:
             res = {k: v.clone() for k, v in res.items()}
+        return res
+
+    # ------------------------------------------------------------------ from camera frames to results at frame size
+    def _device(self):
+        return next(self.model.parameters()).device
+
+    @staticmethod
+    def _upload_frame(frame, device):
+        """A host frame reaches the device through pinned memory, without blocking; a device frame is used where it is."""
+        if frame.device == device:
+            return frame
+        if device.type == "cuda" and frame.device.type == "cpu":
+            frame = frame.pin_memory()
+        return frame.to(device, non_blocking=True)
+
+    def predict_frames(self, frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False):
+        """Decoded camera frames in, results at each frame's own size out.  frames: list of uint8 (h,w,3) tensors, host or device,
+        of any sizes: at most hip.AUGMENT_BATCH (16) per call, half that with ensemble=True (the forward batch is 2B); no side
+        above 16384.  The reference's evaluation transform (RandomResize([size], max_size), ToTensor, Normalize:
+        src/datasets/coco.py:84-91) runs on the device (DeviceAugment(train=False) + device_collate(pad_to=pad_to)), the forward
+        is predict()'s (one graph per (B or 2B, H, W)), and ONE kernel (gwd_dense_postprocess_resized) brings depth, millimetres
+        and labels back to frame size: bilinear by F.interpolate(align_corners=False)'s rule over the un-padded network region.
+        ensemble=True: the prediction of the mirrored frame, mirrored back, is averaged in (depth: mean; logits: sum) - the
+        mirrored copies ride in the same resize launches and the same forward.
+
+        -> RESULT_KEYS + "net_sizes": depth / depth_mm / labels (B, Fh, Fw) with (Fh, Fw) the largest frame of the call (outside
+        a frame 0 / 0 / 255), sizes (B,2) the FRAME sizes, net_sizes (B,2) the un-padded network sizes, scores / lines / order /
+        count as predict() gives them for the B frames, lines in frame pixels.  The dense results, sizes and net_sizes are fresh
+        tensors on every call; the four line results follow copy= as in predict() (LIFETIME OF OUTPUTS).  No host sync."""
+        B = len(frames)
+        limit = hip.AUGMENT_BATCH // 2 if ensemble else hip.AUGMENT_BATCH
+        if not 0 < B <= limit:
+            raise ValueError("predict_frames: 1..%d frames per call%s, got %d" % (limit, " with ensemble=True" if ensemble else "", B))
+        for f in frames:
+            if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or 0 in f.shape:
+                raise ValueError("predict_frames: frames are uint8 (h, w, 3) tensors")
+        dev = self._device()
+        aug = data.DeviceAugment(train=False, test_size=size, max_size=max_size)
+        frame_sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
+        net_sizes = [data.resized_shape(w, h, size, max_size) for h, w in frame_sizes]
+        if max(max(s) for s in frame_sizes + net_sizes) > 16384:
+            raise ValueError("predict_frames: frame and network sizes are limited to 16384 per side")
+        on_dev = [self._upload_frame(f, dev) for f in frames]
+        params = [aug.params(w, h) for h, w in frame_sizes]
+        if ensemble:                                       # the flip rides in the resize's read; collated behind the originals
+            on_dev, params = on_dev * 2, params + [dict(p, flip="h") for p in params]
+        no_lines = torch.zeros((0, 4))
+        out, table = data.DeviceAugment.apply_batch([(f, None, None) for f in on_dev], [no_lines] * len(on_dev), params,
+                                                    carry=np.asarray([frame_sizes, frame_sizes, net_sizes], dtype=np.int32))
+        batch = data.device_collate([o[:3] for o in out], device=dev, dtype=self.compute_dtype, pad_to=pad_to)
+        fsz, nsz = table[0], table[2]                      # the lines of all 2B images are scaled to their frame's size
+        raw, post = self._run(NestedTensor(batch["images"], batch["pad_mask"]), table[:2].view(2 * B, 2) if ensemble else fsz, True)
+        with torch.no_grad(), self._on_stream():
+            depth, mm, labels = ops.dense_postprocess_resized(
+                raw["pred_depth"][-1], raw["pred_seg"], nsz, fsz, (max(s[0] for s in frame_sizes), max(s[1] for s in frame_sizes)),
+                self.min_depth, self.max_depth, twin=B if ensemble else 0)
+        res = {"depth": depth, "depth_mm": mm, "labels": labels, "sizes": fsz, "net_sizes": nsz}
+        for k in ("scores", "lines", "order", "count"):
+            res[k] = post[k][:B].clone() if copy else post[k][:B]
         return res

@@ -1966,6 +1966,35 @@ def dense_postprocess(depth, seg, sizes=None, min_depth=1e-3, max_depth=10.0, wi
     return out
 
 
+def dense_postprocess_resized(depth, seg, sizes, frame_sizes, out_hw, min_depth=1e-3, max_depth=10.0, twin=0, with_mm=True, out=None):
+    """dense_postprocess at another size per image, in one pass (gwd_dense_postprocess_resized): the un-padded (h, w) region of
+    image b (sizes (B,2) int32 on the device, None = all of H x W) is resized to frame_sizes[b] = (fh, fw) (device int32) by
+    F.interpolate(mode="bilinear", align_corners=False)'s rule inside outputs of out_hw = (Fh, Fw) >= every frame; the rest is
+    0 / 0 / 255.  twin > 0: depth / seg hold B + twin images and image b + twin is the prediction for the mirrored image b, which
+    is mirrored back and averaged in (depth: mean of the clamped values; logits: sum).  H, W, Fh, Fw <= 16384.
+    -> (depth fp32 (B,Fh,Fw), depth_mm uint16 or None, labels uint8); out = the three tensors of an earlier call."""
+    if seg.dim() != 4 or seg.shape[1] != 2:
+        raise ValueError("seg must be (B, 2, H, W) logits, got %s" % (tuple(seg.shape),))
+    Bs, _, H, W = seg.shape
+    twin = int(twin)
+    B = Bs - twin
+    if twin < 0 or B <= 0 or (twin and twin != B):
+        raise ValueError("twin must be 0 or half of the %d source images, got %d" % (Bs, twin))
+    if depth.numel() != Bs * H * W:
+        raise ValueError("depth %s and seg %s differ" % (tuple(depth.shape), tuple(seg.shape)))
+    Fh, Fw = (int(v) for v in out_hw)
+    depth = depth.reshape(Bs, H, W).contiguous()
+    if H > 1 and seg.stride(2) != W * seg.stride(3):
+        seg = seg.contiguous()
+    if out is None:
+        out = (torch.empty((B, Fh, Fw), dtype=torch.float32, device=depth.device),
+               torch.empty((B, Fh, Fw), dtype=torch.uint16, device=depth.device) if with_mm else None,
+               torch.empty((B, Fh, Fw), dtype=torch.uint8, device=depth.device))
+    _lib().dense_postprocess_resized(depth, seg, (seg.stride(0), seg.stride(3), seg.stride(1)), sizes, frame_sizes, twin, out[0], out[1],
+                                     out[2], B, H, W, Fh, Fw, min_depth, max_depth)
+    return out
+
+
 def line_postprocess(logits, lines, sizes, thresh=0.6):
     """PostProcess_Line 'prediction' for two classes plus a ranking (gwd_line_postprocess): logits (B,Q,2), lines (B,Q,4|6),
     sizes (B,2) int32 (h, w) -> scores (B,Q), lines in pixels (B,Q,4), order (B,Q) int32 (score descending, equal scores by

@@ -539,6 +539,29 @@ int gwd_dense_postprocess(const void *depth, const void *seg_logits, int64_t seg
                           const int32_t *sizes, float *depth_out, uint16_t *depth_mm, uint8_t *label, int32_t B, int32_t H,
                           int32_t W, float min_depth, float max_depth, int32_t depth_dtype, int32_t seg_dtype, void *stream);
 
+/* gwd_dense_postprocess with a bilinear resize to a per-image output size and an optional mirrored twin (the horizontal-mirror
+ * ensemble of depth evaluation), one streaming launch, every output element written, no memset, no atomics.
+ *   depth [Bs][H][W], seg_logits (strides as above) with Bs = B + twin source images; sizes [B][2] int32 = the un-padded (h, w) of
+ *   each image (NULL = H x W) and frame_sizes [B][2] int32 = its output (fh, fw), both DEVICE data (values outside the allocated
+ *   extents are clamped to them); twin = 0: no ensemble; twin > 0: image b's twin is source image b + twin, of the same (h, w);
+ *   Fh, Fw: the allocated output extent, fh <= Fh, fw <= Fw.
+ *   depth_out [B][Fh][Fw] fp32, depth_mm [B][Fh][Fw] uint16 (may be NULL), label [B][Fh][Fw] uint8.
+ * Source sample at (y, x), y < h, x < w: s = san(depth[b][y][x]), san = the clamp above; with a twin
+ * s = 0.5f * (san(depth[b][y][x]) + san(depth[b + twin][y][w - 1 - x])) and the logits are the sums of the two, class by class.
+ * Resize: F.interpolate(mode = "bilinear", align_corners = False) over the un-padded h x w region (padding is never read), down-
+ * scaling by the same rule (no anti-aliasing), with exact integer coordinates: n = max((2 d + 1) h - fh, 0), i0 = n / (2 fh),
+ * lambda = float(n % (2 fh)) / float(2 fh), i1 = min(i0 + 1, h - 1), and the same along x; rows are blended first, then columns,
+ * each as (1 - lambda) a + lambda b in fp32; a tap of weight zero does not enter (its NaN or inf stays out).
+ * Inside (fh, fw): depth_out = the interpolated s kept inside [min, max], depth_mm = rint(depth_out * 1000) saturated, label = argmax of the interpolated
+ * logits by the rules above.  Outside: 0 / 0 / 255.  fh == h, fw == w, twin == 0 gives gwd_dense_postprocess bit for bit.
+ * 8 pixels per thread (16-byte stores) when Fw % 8 == 0 and the outputs are 16-byte aligned (label: 8), one pixel otherwise;
+ * 16-byte source loads when W % 8 == 0, the logits are interleaved or planar as above and the sources are 16-byte aligned.
+ * -1 on bad arguments, among them any of H, W, Fh, Fw above 16384.                                                           */
+int gwd_dense_postprocess_resized(const void *depth, const void *seg_logits, int64_t seg_sb, int64_t seg_sp, int64_t seg_sc,
+                                  const int32_t *sizes, const int32_t *frame_sizes, int32_t twin, float *depth_out,
+                                  uint16_t *depth_mm, uint8_t *label, int32_t B, int32_t H, int32_t W, int32_t Fh, int32_t Fw,
+                                  float min_depth, float max_depth, int32_t depth_dtype, int32_t seg_dtype, void *stream);
+
 /* PostProcess_Line 'prediction' for two classes (src/models/glassrgbd.py:470-477) plus a ranking, one workgroup per image.
  *   logits [B][Q][2] fp32, lines [B][Q][ld] fp32 with ld 4 or 6, sizes [B][2] int32 (h, w), thresh;
  *   scores [B][Q] fp32 = softmax probability of class 0 (the labels are all 0), lines_px [B][Q][4] fp32 (16-byte aligned) = the
