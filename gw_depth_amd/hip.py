@@ -37,6 +37,7 @@ ENTRY_POINTS = [
     "gwd_dense_postprocess", "gwd_line_postprocess", "gwd_line_score",
     "gwd_dense_postprocess_resized",
     "gwd_resample_u8_pass_batch", "gwd_gather2d_batch", "gwd_color_adjust_batch",
+    "gwd_pyr_tail_forward", "gwd_pyr_tail_backward", "gwd_pyr_tail_fold_wgrad",
 ]
 
 
@@ -274,6 +275,10 @@ class HipLibrary:
         L.gwd_window_map_multi.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         L.gwd_sqnorm.argtypes = [vp, vp, i64, vp]
         L.gwd_adamw_step.argtypes = [vp, vp, vp, vp, vp, vp, i64] + [f32] * 9 + [vp]
+        pvp, pi32 = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32)
+        L.gwd_pyr_tail_forward.argtypes = [vp, pvp, pi32, pi32, i32] + [vp] * 6 + [i32] * 6 + [vp]
+        L.gwd_pyr_tail_backward.argtypes = [vp, pvp, pi32, pi32, i32] + [i32] * 5 + [vp]
+        L.gwd_pyr_tail_fold_wgrad.argtypes = [vp, pvp, i32, vp, i32, i32, i32, vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -775,6 +780,53 @@ class HipLibrary:
                 or not (D.is_contiguous() and dw.is_contiguous()):
             raise ValueError("upsample_taps_fold: D (Cin,4,4,Cout) fp32 -> dw (Cout,3,3,Cin) fp32, both contiguous")
         self._check(self.lib.gwd_upsample_taps_fold(_ptr(D), _ptr(dw), Cout, Cin, self._stream(D, dw)), "gwd_upsample_taps_fold")
+
+    PYR_MAX_BRANCHES = 4
+
+    @staticmethod
+    def _pyr_branches(maps, B, N, like):
+        """Pointer / size arrays of the product maps (B,h_k,w_k,9,N) of gwd_pyr_tail_forward / _backward."""
+        if not 1 <= len(maps) <= HipLibrary.PYR_MAX_BRANCHES:
+            raise ValueError("pyr_tail: 1 to %d low-resolution branches, got %d" % (HipLibrary.PYR_MAX_BRANCHES, len(maps)))
+        for m in maps:
+            if m.dim() != 5 or m.shape[0] != B or m.shape[3] != 9 or m.shape[4] != N or m.dtype != like.dtype or not m.is_contiguous():
+                raise ValueError("pyr_tail: a product map is (B,h,w,9,N) contiguous in the map's dtype, got %r" % (tuple(m.shape),))
+        ptrs = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
+        hk = (ctypes.c_int32 * len(maps))(*[m.shape[1] for m in maps])
+        wk = (ctypes.c_int32 * len(maps))(*[m.shape[2] for m in maps])
+        return ptrs, hk, wk
+
+    def pyr_tail_forward(self, part, Zs, gamma, beta, z, y, mean, rstd, gelu):
+        """y = [GELU](LayerNorm(part + the bilinear gather of the product maps Zs)), mean, rstd; z (or None) receives the sum itself
+        (gwd_pyr_tail_forward).  False when the library has no kernel for the shape (nothing was launched)."""
+        B, H, W, N = part.shape
+        ptrs, hk, wk = self._pyr_branches(Zs, B, N, part)
+        rc = self.lib.gwd_pyr_tail_forward(_ptr(part), ptrs, hk, wk, len(Zs), _ptr(gamma), _ptr(beta), _ptr(z), _ptr(y), _ptr(mean), _ptr(rstd),
+                                           B, H, W, N, int(bool(gelu)), dtype_code(part), self._stream(part, y, *Zs))
+        if rc == -4:
+            return False
+        self._check(rc, "gwd_pyr_tail_forward")
+        return True
+
+    def pyr_tail_backward(self, gz, Gs):
+        """Gs[k] (B,h_k,w_k,9,N) = the gradient of the product map Z_k from gz (B,H,W,N) (gwd_pyr_tail_backward)."""
+        B, H, W, N = gz.shape
+        ptrs, hk, wk = self._pyr_branches(Gs, B, N, gz)
+        self._check(self.lib.gwd_pyr_tail_backward(_ptr(gz), ptrs, hk, wk, len(Gs), B, H, W, N, dtype_code(gz), self._stream(gz, *Gs)),
+                    "gwd_pyr_tail_backward")
+
+    def pyr_tail_fold_wgrad(self, d_hi, d_low, dw, C2):
+        """dw (N,3,3,(1+nbr) C2) fp32 += d_hi (N,3,3,(1+nbr-nlow) C2) and the low branches' d_low[k] (9 N, C2) (gwd_pyr_tail_fold_wgrad)."""
+        N, Cw, nlow = dw.shape[0], dw.shape[-1], len(d_low)
+        nbr = Cw // C2 - 1
+        ok = dw.dtype == torch.float32 and dw.is_contiguous() and tuple(dw.shape) == (N, 3, 3, (1 + nbr) * C2) and 1 <= nlow <= nbr \
+            and d_hi.dtype == torch.float32 and d_hi.is_contiguous() and d_hi.numel() == N * 9 * (1 + nbr - nlow) * C2 \
+            and all(d.dtype == torch.float32 and d.is_contiguous() and d.numel() == 9 * N * C2 for d in d_low)
+        if not ok:
+            raise ValueError("pyr_tail_fold_wgrad: contiguous fp32 tensors in the documented shapes expected")
+        ptrs = (ctypes.c_void_p * nlow)(*[d.data_ptr() for d in d_low])
+        self._check(self.lib.gwd_pyr_tail_fold_wgrad(_ptr(d_hi), ptrs, nlow, _ptr(dw), N, C2, nbr, self._stream(d_hi, dw, *d_low)),
+                    "gwd_pyr_tail_fold_wgrad")
 
     def tokattn_pair_forward(self, q, q2, k, v, o, o2, scale):
         """Both class tokens against the same k / v in one launch (bf16): q, q2 -> o, o2.  False when the library declines the

@@ -660,7 +660,12 @@ class PyramidLayer(nn.Module):
             x = F.pad(x, (0, 0, 0, max(self.pools[0] - W, 0), 0, max(self.pools[0] - H, 0)))
         x, pooled = ops.psp_pools(x, self.pools)                  # the four average pools in one pass
         ys = [getattr(self, f"branch{i}")[1](p, True) for i, p in enumerate(pooled, start=1)]
-        x = self.lastconv[0](ops.pyramid_concat(x, ys), True)      # the up-sampling kernels write the concat's channel slices
+        tail = self.lastconv[0]
+        if ops.PYRAMID_TAIL_LOWRES and tuple(self.pools) == (16, 8, 4, 2) and ops.pyramid_tail_supported(x, ys, tail.conv.weight):
+            # the coarse branches are convolved at their own resolution, only [x | up(pool 2)] at this one (ops._PyramidTailFn)
+            x = ops.pyramid_tail(x, ys, tail.conv.weight, tail.layer_norm.weight, tail.layer_norm.bias, True)
+        else:
+            x = tail(ops.pyramid_concat(x, ys), True)               # the up-sampling kernels write the concat's channel slices
         return ops.conv2d(x, self.lastconv[2].weight)
 
     def forward_padded(self, x, c):

@@ -1311,6 +1311,134 @@ def pyramid_concat(x, ys):
     return _PyramidCatFn.apply(x, *ys)
 
 
+PYRAMID_TAIL_LOWRES = True       # PyramidLayer's last ConvLn: convolve the coarse PSP branches at their own resolution (pyramid_tail)
+PYRAMID_TAIL_NLOW = 3            # how many of the branches (coarsest first) go that way; the rest stay in the high-resolution concat
+
+
+class _Ctx:
+    """Stands in for an autograd context where a Function's forward / backward pair is reused inside another Function."""
+
+
+class _PyramidTailFn(torch.autograd.Function):
+    """[GELU](LayerNorm(conv3x3([x | up(y_1) | ... | up(y_n)], w))) without convolving the up-sampled coarse branches at full
+    resolution.  conv and the bilinear resize are linear and the channel mixing commutes with the resize:
+        conv3x3(up(y))(p) = sum_tap [p + tap inside] up(W_tap . y)(p + tap),
+    so the first nlow branches get their nine channel products as ONE 1x1 convolution on their own pixels (y_k -> Z_k, 9 N
+    channels); the 3x3 convolution runs on [x | the other branches] only and gwd_pyr_tail_forward adds the bilinear gather of the
+    Z_k and normalises.  Backward is the transpose: gwd_layernorm_backward, the high-resolution data / weight gradient,
+    gwd_pyr_tail_backward (gz -> the gradient of every Z_k) and the 1x1 gradients; the partial weight gradients are folded into
+    the one parameter's layout by gwd_pyr_tail_fold_wgrad."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, gelu, nlow, w_sink, ln_sinks, *ys):
+        lib = _lib()
+        B, H, W, C2 = x.shape
+        N = w.shape[0]
+        nbr = len(ys)
+        if tuple(w.shape) != (N, 3, 3, (1 + nbr) * C2) or not 1 <= nlow <= nbr:
+            raise ValueError("pyramid_tail: weight %r does not fit %d branches of %d channels" % (tuple(w.shape), nbr, C2))
+        dt = x.dtype
+        lows = [y.contiguous() for y in ys[:nlow]]
+        cctx = _Ctx()
+        cat = _PyramidCatFn.forward(cctx, x, *ys[nlow:]) if nlow < nbr else x.contiguous()
+        Chi = cat.shape[-1]
+        w_hi = derived_weight(w, ("pyr_tail_hi", nlow), lambda: torch.cat([w.detach()[..., :C2], w.detach()[..., (1 + nlow) * C2:]], dim=-1))
+        w_lo = [derived_weight(w, ("pyr_tail_lo", k), lambda k=k: w.detach()[..., (k + 1) * C2:(k + 2) * C2].permute(1, 2, 0, 3)
+                               .reshape(9 * N, 1, 1, C2).contiguous()) for k in range(nlow)]
+        part = torch.empty((B, H, W, N), dtype=dt, device=x.device)
+        dims = (B, H, W, Chi, H, W, N, 3, 3)
+        lib.conv_forward(cat, _weight_for(w_hi, None, dt), part, dims, stride=1, pad=1)
+        Zs = []
+        for y, wl in zip(lows, w_lo):
+            h, wd = y.shape[1], y.shape[2]
+            Z = torch.empty((B, h, wd, 9, N), dtype=dt, device=x.device)
+            lib.conv_forward(y, _weight_for(wl, None, dt), Z.view(B, h, wd, 9 * N), (B, h, wd, C2, h, wd, 9 * N, 1, 1), stride=1, pad=0)
+            Zs.append(Z)
+        need_grad = any(ctx.needs_input_grad)
+        out = torch.empty_like(part)
+        z = torch.empty_like(part) if need_grad else None           # inference: the sum itself is never written
+        mean = torch.empty(B * H * W, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(B * H * W, dtype=torch.float32, device=x.device)
+        g, b = gamma.detach(), beta.detach()
+        if lib.pyr_tail_forward(part, Zs, g, b, z, out, mean, rstd, gelu) is False:
+            raise ValueError("pyramid_tail: no kernel for N = %d with branches %r" % (N, [tuple(y.shape[1:3]) for y in lows]))
+        if need_grad:
+            ctx.save_for_backward(cat, w, z, g, b, mean, rstd, *lows)
+        ctx.cfg = (dims, bool(gelu), nlow, nbr, C2, w_sink, ln_sinks, cctx, w_hi, w_lo)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = _lib()
+        cat, w, z, g, b, mean, rstd, *lows = ctx.saved_tensors
+        dims, gelu, nlow, nbr, C2, w_sink, ln_sinks, cctx, w_hi, w_lo = ctx.cfg
+        B, H, W, Chi, _, _, N, _, _ = dims
+        dt = cat.dtype
+        rows = B * H * W
+        gz = torch.empty_like(z)
+        dg = db = None
+        if ln_sinks is not None:
+            (dg, h1), (db, h2) = ln_sinks
+        else:
+            dg = torch.zeros(N, dtype=torch.float32, device=z.device)
+            db = torch.zeros(N, dtype=torch.float32, device=z.device)
+        lib.layernorm_backward(gy.contiguous(), z, g, b, mean, rstd, gz, dg, db, rows, N, gelu)
+        if ln_sinks is not None:
+            for h in (h1, h2):
+                if h is not None:
+                    h()
+        # ---- high-resolution part: data gradient of [x | the remaining branches], then the concat's own backward
+        g_cat = torch.empty_like(cat)
+        lib.conv_forward(gz, _weight_transposed(w_hi, None, dt), g_cat, (B, H, W, N, H, W, Chi, 3, 3), stride=1, pad=1, gather=GATHER_TRANSPOSED)
+        g_high = list(_PyramidCatFn.backward(cctx, g_cat)) if nlow < nbr else [g_cat]
+        # ---- low-resolution part: the gradients of the product maps, then the 1x1 data gradients
+        Gs = [torch.empty((B, y.shape[1], y.shape[2], 9, N), dtype=dt, device=z.device) for y in lows]
+        lib.pyr_tail_backward(gz, Gs)
+        g_low = []
+        for y, G, wl in zip(lows, Gs, w_lo):
+            h, wd = y.shape[1], y.shape[2]
+            gyk = torch.empty_like(y)
+            lib.conv_forward(G.view(B, h, wd, 9 * N), _weight_transposed(wl, None, dt), gyk, (B, h, wd, 9 * N, h, wd, C2, 1, 1), stride=1, pad=0,
+                             gather=GATHER_TRANSPOSED)
+            g_low.append(gyk)
+        # ---- weight gradients: each part in its own shape, folded into the parameter's layout once all have been issued
+        gw = None
+        if ctx.needs_input_grad[1]:
+            d_hi = WGRADS.scratch((N, 3, 3, Chi), z.device)
+            d_lo = [WGRADS.scratch((9 * N, 1, 1, C2), z.device) for _ in lows]
+            if w_sink is None:
+                gw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
+            dst = gw if w_sink is None else w_sink[0].view(w.shape)
+
+            def fold(d_hi=d_hi, d_lo=d_lo, dst=dst, hook=None if w_sink is None else w_sink[1]):
+                lib.pyr_tail_fold_wgrad(d_hi, d_lo, dst, C2)
+                if hook is not None:
+                    hook()
+
+            WGRADS.add(cat, gz, d_hi, dims, dict(stride=1, pad=1))
+            for i, (y, G, d) in enumerate(zip(lows, Gs, d_lo)):
+                h, wd = y.shape[1], y.shape[2]
+                WGRADS.add(y, G.view(B, h, wd, 9 * N), d, (B, h, wd, C2, h, wd, 9 * N, 1, 1), dict(stride=1, pad=0),
+                           fold if i == len(lows) - 1 else None)
+        grads = g_high[:1] + [gw] + ([None, None] if ln_sinks is not None else [dg, db]) + [None] * 4 + g_low + g_high[1:]
+        return tuple(grads)
+
+
+def pyramid_tail_supported(x, ys, w):
+    """The shapes gwd_pyr_tail_forward / _backward take (PyramidLayer picks the route with this)."""
+    N, C2 = w.shape[0], x.shape[-1]
+    return (x.is_cuda and not getattr(_lib(), "is_fake", False) and x.dtype in (torch.float32, torch.bfloat16) and C2 % 8 == 0
+            and N % 32 == 0 and N <= 320 and len(ys) > PYRAMID_TAIL_NLOW >= 1 and tuple(w.shape[1:]) == (3, 3, (1 + len(ys)) * C2))
+
+
+def pyramid_tail(x, ys, w, gamma, beta, gelu=False, nlow=None):
+    """x (B,H,W,C2), ys[k] (B,h_k,w_k,C2) coarsest first, w (N,3,3,(1+len(ys)) C2) fp32 master, gamma / beta (N,) ->
+    [GELU](LayerNorm(conv3x3(pyramid_concat(x, ys), w))): see _PyramidTailFn."""
+    sg, sb = _sink(gamma), _sink(beta)
+    ln_sinks = (sg, sb) if (sg is not None and sb is not None) else None
+    return _PyramidTailFn.apply(x, w, gamma, beta, bool(gelu), int(PYRAMID_TAIL_NLOW if nlow is None else nlow), _sink(w), ln_sinks, *ys)
+
+
 def upsample_bilinear_ac(x, size):
     """(B,Hs,Ws,C) -> (B,H,W,C), bilinear with align_corners=True."""
     return _ResampleFn.apply(x, tuple(size), hip.RESAMPLE_BILINEAR_AC)

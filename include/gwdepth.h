@@ -487,6 +487,28 @@ int gwd_psp_pool_forward(const void *x, void *p16, void *p8, void *p4, void *p2,
                          int32_t dtype, void *stream);
 int gwd_psp_pool_backward(const void *g_pass, const void *g16, const void *g8, const void *g4, const void *g2, void *gx, int32_t B,
                           int32_t H, int32_t W, int32_t C, int32_t ldg, int32_t dtype, void *stream);
+/* Low-resolution tail of the PSP module (the 3x3 ConvLn over [x | up(y_1) | ...], points_sample.py:114-125).  A convolution and
+ * the align-corners bilinear resize `up` are both linear, so  conv3x3(up(y))(p) = sum_tap [p + tap inside] up(W_tap . y)(p + tap):
+ * the caller forms the nine channel products of a branch on its low-resolution pixels, Z_k (B,h_k,w_k,9,N) = a 1x1 convolution of
+ * y_k with the weight slice as (9 N, C), taps in the weight's order, and convolves only [x | the remaining branches] at (H, W).
+ *   forward:  z = part + sum_k sum_tap [p + tap inside] bilinear_ac(Z_k[.., tap, :])(p + tap),  y = [GELU](LayerNorm(z) gamma + beta);
+ *             part (B,H,W,N) is the high-resolution convolution's output; z (may be NULL: not stored), mean, rstd [B*H*W] are
+ *             exactly what gwd_layernorm_backward takes (statistics of z as stored, two passes, eps 1e-5); fp32 accumulation.
+ *   backward: G_k (B,h_k,w_k,9,N) = the gradient of Z_k from gz (B,H,W,N): every element is one gather over its pixel's footprint,
+ *             summed in a fixed order (no atomics: bit-reproducible).
+ *   fold:     dw (N,3,3,(1+nbr) C2) fp32 += d_hi (N,3,3,(1+nbr-nlow) C2), the weight gradient of the high-resolution part (x and the
+ *             last nbr - nlow branches), and d_low[k] (9 N, C2), the 1x1 weight gradients of the first nlow branches.
+ * 1 <= nb <= GWD_PYR_MAX_BRANCHES, h_k <= H, w_k <= W (h_k == 1: every pixel reads row 0).  -4 (nothing launched): N not a multiple
+ * of 32 (backward: 8) or above 320, or a branch so fine that an 8x8 tile and its ring reach more than 5 of its rows or columns.  No allocation, no
+ * memset, no host synchronisation: all three may be captured.                                                              */
+#define GWD_PYR_MAX_BRANCHES 4
+int gwd_pyr_tail_forward(const void *part, const void *const *Z, const int32_t *hk, const int32_t *wk, int32_t nb,
+                         const float *gamma, const float *beta, void *z, void *y, float *mean, float *rstd, int32_t B,
+                         int32_t H, int32_t W, int32_t N, int32_t gelu, int32_t dtype, void *stream);
+int gwd_pyr_tail_backward(const void *gz, void *const *G, const int32_t *hk, const int32_t *wk, int32_t nb, int32_t B, int32_t H,
+                          int32_t W, int32_t N, int32_t dtype, void *stream);
+int gwd_pyr_tail_fold_wgrad(const float *d_hi, const float *const *d_low, int32_t nlow, float *dw, int32_t N, int32_t C2,
+                            int32_t nbr, void *stream);
 int gwd_avgpool_forward(const void *x, void *y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
                         int32_t dtype, void *stream);
 int gwd_avgpool_backward(const void *gy, void *gx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
