@@ -98,19 +98,17 @@ class Bottleneck(nn.Module):
         """gated_in: x is the previous block's output and that block left its ReLU backward to us (defer_out there); inside the block
         conv1 -> conv2 -> conv3 hand theirs on the same way (ops.conv2d: defer / in_gate), so a block's three activation-backward
         passes run in the data-gradient epilogues of the layers behind them."""
-        g = ACT_RELU if ops.act_gate_enabled() else ACT_NONE
-        d = g != ACT_NONE
         s, b = self.bn1.folded()
         out, x = ops.conv2d(x, self.conv1.weight, row_scale=s, shift=b, act=ACT_RELU, fanout=True,     # x again, for the skip path
-                            in_gate=ACT_RELU if gated_in else ACT_NONE, defer=d)
+                            in_gate=ACT_RELU if gated_in else ACT_NONE, defer=True)
         s, b = self.bn2.folded()
-        out = ops.conv2d(out, self.conv2.weight, stride=self.stride, pad=1, row_scale=s, shift=b, act=ACT_RELU, in_gate=g, defer=d)
+        out = ops.conv2d(out, self.conv2.weight, stride=self.stride, pad=1, row_scale=s, shift=b, act=ACT_RELU, in_gate=ACT_RELU, defer=True)
         idt = x
         if self.downsample is not None:
             s, b = self.downsample[1].folded()
             idt = ops.conv2d(x, self.downsample[0].weight, stride=self.stride, row_scale=s, shift=b)
         s, b = self.bn3.folded()
-        return ops.conv2d(out, self.conv3.weight, row_scale=s, shift=b, residual=idt, act=ACT_RELU, in_gate=g, defer=defer_out)
+        return ops.conv2d(out, self.conv3.weight, row_scale=s, shift=b, residual=idt, act=ACT_RELU, in_gate=ACT_RELU, defer=defer_out)
 
 
 class ResNetBody(nn.Module):
@@ -140,11 +138,10 @@ class ResNetBody(nn.Module):
         feats = []
         # a block whose output feeds only the next block of its layer defers its last ReLU backward to that block's first conv
         # (which, with the fan-out, is the single consumer of the map); the last block's output also leaves as a feature level
-        chain = ops.act_gate_enabled()
         for li in range(1, 5):
             blocks = getattr(self, f"layer{li}")
             for bi, blk in enumerate(blocks):
-                x = blk(x, gated_in=chain and bi > 0, defer_out=chain and bi + 1 < len(blocks))
+                x = blk(x, gated_in=bi > 0, defer_out=bi + 1 < len(blocks))
             feats.append(x)
         return feats
 
@@ -916,14 +913,13 @@ class DensePrediction(nn.Module):
         f = cast("decoder_up1", f)
         # the ELU backward of three of the four convolutions runs inside the backward of the layer behind each: the LayerNorm (upconv1),
         # the footprint sum of the up-sampling conv (conv1), the data-gradient epilogue of conv2 (upconv2)
-        g = ACT_ELU if ops.act_gate_enabled() else ACT_NONE
-        u1 = getattr(self, f"norm_{tag}")(getattr(self, f"upconv1_{tag}")(f, (2 * H, 2 * W), defer=g != ACT_NONE), in_gate=g)
-        c1 = ops.conv2d(u1, getattr(self, f"conv1_{tag}")[0].weight, pad=1, act=ACT_ELU, defer=g != ACT_NONE)
+        u1 = getattr(self, f"norm_{tag}")(getattr(self, f"upconv1_{tag}")(f, (2 * H, 2 * W), defer=True), in_gate=ACT_ELU)
+        c1 = ops.conv2d(u1, getattr(self, f"conv1_{tag}")[0].weight, pad=1, act=ACT_ELU, defer=True)
         c1 = cast("decoder_up2", c1)
-        u2 = getattr(self, f"upconv2_{tag}")(c1, size, defer=g != ACT_NONE, in_gate=g)
+        u2 = getattr(self, f"upconv2_{tag}")(c1, size, defer=True, in_gate=ACT_ELU)
         # conv2 keeps its own pass: in the 1- / 2-channel heads' data gradient (one thread per pixel, 64 bytes of gate each) the gate
         # costs 90-140 us inside the step against the 87 us of the pass it would replace (tools/gatebench.py, per-kernel trace)
-        return cast("decoder_head", ops.conv2d(u2, getattr(self, f"conv2_{tag}")[0].weight, pad=1, act=ACT_ELU, in_gate=g))
+        return cast("decoder_head", ops.conv2d(u2, getattr(self, f"conv2_{tag}")[0].weight, pad=1, act=ACT_ELU, in_gate=ACT_ELU))
 
     def forward(self, feat, depth3, dtok, stok, size, cast=None):
         cast = cast or (lambda stage, t: t)

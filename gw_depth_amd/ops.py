@@ -436,6 +436,65 @@ def _padded_weight_for(w, geom, kind, dtype):
     return padded_weight(w.detach(), geom, kind, dtype)
 
 
+def _fan_in(ctx, g_fan):
+    """The second gradient of a fan-out node (the one of its `x again` output, see _ConvFn.forward), contiguous; None where the node
+    has no such output or nothing arrived for it."""
+    return g_fan[0].contiguous() if (ctx.fan and g_fan and g_fan[0] is not None) else None
+
+
+def _dgrad_dims(dims):
+    """dims of a convolution -> dims of its data gradient: the same problem with the input and the output side swapped."""
+    B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW = dims
+    return (B, Ho, Wo, Cout, Hi, Wi, Cin, KH, KW)
+
+
+def _dgrad_stride1(dv, wt, x, dims, pad, g_in=None):
+    """Data gradient of a stride-1 convolution of x (dims): the transposed gather of dv over the [Cin][taps][Cout] weights wt; g_in, the
+    input's second gradient (fan-out), joins in the kernel epilogue."""
+    gx = torch.empty_like(x)
+    _lib().conv_forward(dv, wt, gx, _dgrad_dims(dims), stride=1, pad=pad, gather=GATHER_TRANSPOSED, residual=g_in)
+    return gx
+
+
+def _conv_wgrad(x, dv, w, dims, kw, sink, geom=None):
+    """Weight gradient of a convolution (kw: its descriptor keywords).  With a sink the kernel ACCUMULATES (fp32 atomics) straight into
+    the flat gradient buffer, no temporary: the job joins WGRADS, sink[1] fires once it has been issued, and autograd gets None; without
+    one the gradient is formed in fresh zeros and returned.  geom = (Np, Cg, Cgp) (_PadConvFn): the gradient is formed in the padded
+    shape, in zeroed scratch, and its real entries are added to the parameter's own shape by gwd_unpad_add_batch."""
+    lib = _lib()
+    if geom is None:
+        if sink is not None:
+            WGRADS.add(x, dv, sink[0], dims, kw, sink[1])
+            return None
+        gw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
+        lib.conv_wgrad(x, dv, gw, dims, **kw)
+        return gw
+    Np, Cg, Cgp = geom
+    N, KH, KW, C = w.shape
+    tmp = WGRADS.scratch((Np, KH, KW, dims[3]), x.device)
+    fold = (N, KH * KW, C // Cg, Cg, Cgp)
+    if sink is not None:
+        WGRADS.add(x, dv, tmp, dims, kw, sink[1], unpad=(sink[0].view(-1),) + fold)
+        return None
+    lib.conv_wgrad(x, dv, tmp, dims, **kw)
+    gw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
+    lib.unpad_add_batch([(tmp, gw.view(-1)) + fold])
+    return gw
+
+
+def _conv_backward_stride1(need_gx, need_gw, x, w, dv, g_in, dims, pad, geom, sink):
+    """Backward of a stride-1 convolution without bias or activation (_PadConvFn, the convolution inside _ConvLnFn) -> (gx, gw)."""
+    gx = gw = None
+    if need_gx:
+        wt = _weight_transposed(w, None, x.dtype) if geom is None else _padded_weight_for(w, geom, "t", x.dtype)
+        gx = _dgrad_stride1(dv, wt, x, dims, pad, g_in)
+    elif g_in is not None:
+        gx = g_in
+    if need_gw:
+        gw = _conv_wgrad(x, dv, w, dims, dict(stride=1, pad=pad), sink, geom)
+    return gx, gw
+
+
 class _PadConvFn(torch.autograd.Function):
     """Stride-1 convolution (no bias, no activation) of a layer whose channel counts are not multiples of the MFMA / LDS-DMA
     granule, run on ZERO-PADDED channel counts: x (B, H, W, G*Cgp) holds G groups of Cg real channels each padded to Cgp with zeros,
@@ -467,30 +526,10 @@ class _PadConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, *g_fan):
-        lib = _lib()
-        g_in = g_fan[0].contiguous() if (ctx.fan and g_fan and g_fan[0] is not None) else None
+        g_in = _fan_in(ctx, g_fan)
         x, w = ctx.saved_tensors
         dims, pad, geom, sink = ctx.cfg
-        B, Hi, Wi, Cin, Ho, Wo, Np, KH, KW = dims
-        _, Cg, Cgp = geom
-        N, C = w.shape[0], w.shape[-1]
-        gy = gy.contiguous()
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            lib.conv_forward(gy, _padded_weight_for(w, geom, "t", x.dtype), gx, (B, Ho, Wo, Np, Hi, Wi, Cin, KH, KW), stride=1, pad=pad,
-                             gather=GATHER_TRANSPOSED, residual=g_in)
-        elif g_in is not None:
-            gx = g_in
-        if ctx.needs_input_grad[1]:
-            tmp = WGRADS.scratch((Np, KH, KW, Cin), x.device)
-            fold = (N, KH * KW, C // Cg, Cg, Cgp)
-            if sink is not None:
-                WGRADS.add(x, gy, tmp, dims, dict(stride=1, pad=pad), sink[1], unpad=(sink[0].view(-1),) + fold)
-            else:
-                lib.conv_wgrad(x, gy, tmp, dims, stride=1, pad=pad)
-                gw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
-                lib.unpad_add_batch([(tmp, gw.view(-1)) + fold])
+        gx, gw = _conv_backward_stride1(ctx.needs_input_grad[0], ctx.needs_input_grad[1], x, w, gy.contiguous(), g_in, dims, pad, geom, sink)
         return gx, gw, None, None, None, None
 
 
@@ -564,126 +603,142 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, *g_fan):
-        lib = _lib()
         if gy is None:                                 # (only where materialize_grads is off: a GELU producer nobody consumed)
             return (None,) * 18
-        g_in = g_fan[0].contiguous() if (ctx.fan and g_fan and g_fan[0] is not None) else None
+        g_in = _fan_in(ctx, g_fan)
         x, w, row_scale, ref, mult, gate_src = ctx.saved_tensors
         dims, stride, pad, act, act_scale, gather, vv, has_bias, has_res = ctx.cfg
-        B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW = dims
         gy = gy.contiguous()
-        g_skip = gy                                    # the post-dropout skip connection gets the incoming gradient as is
-        rows = B * Ho * Wo
         w_sink, b_sink = ctx.sinks if ctx.sinks is not None else (None, None)
-        bias_done = False
-        dv = None
-        if mult is not None and has_bias and ctx.needs_input_grad[2] and b_sink is not None:
-            # dropout multiplier, activation backward and the bias gradient in ONE pass (was: an ATen multiply, then the rest)
-            dv = torch.empty_like(gy)
-            bias_done = lib.act_backward_colsum(gy, ref, dv, b_sink[0], rows, Cout, act, act_scale, mult=mult)
-            if bias_done:
-                if b_sink[1] is not None:
-                    b_sink[1]()
-            else:
-                dv = None
-        if ctx.defer:
-            dv = gy                                    # the consumer's data-gradient epilogue has applied act'(.) already
-        if dv is None:
-            if mult is not None:
-                gy = gy * mult
-            if act != ACT_NONE or act_scale != 1.0:
-                dv = torch.empty_like(gy)
-                if has_bias and ctx.needs_input_grad[2] and b_sink is not None:
-                    # activation backward and the bias gradient (column sums of dv) in one pass, straight into the flat gradient
-                    bias_done = lib.act_backward_colsum(gy, ref, dv, b_sink[0], rows, Cout, act, act_scale)
-                    if bias_done and b_sink[1] is not None:
-                        b_sink[1]()
-                if not bias_done:
-                    lib.act_backward(gy, ref, dv, None, rows, Cout, act, act_scale)
-            else:
-                dv = gy
-        gx = gw = gb = None
+        want_b = has_bias and ctx.needs_input_grad[2]
+        dv, bias_done = _conv_act_backward(gy, ref, mult, act, act_scale, ctx.defer, b_sink if want_b else None, dims)
+        gx = g_in
         if ctx.needs_input_grad[0]:
-            wt = _weight_transposed(w, row_scale, x.dtype)
-            gate = dict(gate=(x if gate_src is None else gate_src), gate_act=ctx.in_gate) if ctx.in_gate != ACT_NONE else {}
-            if (gather == GATHER_UPSAMPLED and x.is_cuda and x.dtype == torch.bfloat16 and KH == 3 and KW == 3
-                    and pad == 1 and vv == (2 * Hi, 2 * Wi) and row_scale is None and (g_in is None or not gate)):
-                # one strided convolution of the gradient with the 4x4 collapse of the weights (see _upsampled_dgrad_weight)
-                gx = torch.empty_like(x)
-                lib.conv_forward(dv, _upsampled_dgrad_weight(w, x.dtype), gx, (B, Ho, Wo, Cout, Hi, Wi, Cin, 4, 4), stride=2, pad=1,
-                                 residual=g_in, **gate)
-            elif gather == GATHER_UPSAMPLED:
-                gxv = torch.empty((B, vv[0], vv[1], Cin), dtype=x.dtype, device=x.device)
-                lib.conv_forward(dv, wt, gxv, (B, Ho, Wo, Cout, vv[0], vv[1], Cin, KH, KW), stride=1, pad=pad,
-                                 gather=GATHER_TRANSPOSED)
-                if gate and g_in is None:              # the gate rides on the footprint sum
-                    gx = _nearest_upsample_backward(gxv, Hi, Wi, gate=x, gate_act=ctx.in_gate)
-                else:
-                    gx = _nearest_upsample_backward(gxv, Hi, Wi)
-                    if g_in is not None:
-                        gx = gx + g_in
-                    if gate:                           # behind the skip gradient: a pass of its own
-                        gated = torch.empty_like(gx)
-                        lib.act_backward(gx, x, gated, None, B * Hi * Wi, Cin, ctx.in_gate, 1.0)
-                        gx = gated
-            else:
-                gx = torch.empty_like(x)
-                done = False
-                if KH == 1 and KW == 1 and stride > 1 and pad == 0 and not gate:
-                    # 1x1 / stride s: only the pixels (s i, s j) get a gradient - a plain GEMM over the OUTPUT pixels, then placement
-                    # (+ the skip gradient) in one pass; the transposed gather spent 3/4 of its work on zero-page products
-                    q = torch.empty((B, Ho, Wo, Cin), dtype=x.dtype, device=x.device)
-                    lib.conv_forward(dv, wt, q, (B, Ho, Wo, Cout, Ho, Wo, Cin, 1, 1), stride=1, pad=0, gather=GATHER_TRANSPOSED)
-                    done = lib.stride_place(q, g_in, gx, stride)
-                if not done:
-                    if lib.conv_forward(dv, wt, gx, (B, Ho, Wo, Cout, Hi, Wi, Cin, KH, KW), stride=stride, pad=pad,
-                                        gather=GATHER_TRANSPOSED, residual=g_in, **gate) is False:
-                        # no kernel with the GELU gate for this shape: the data gradient, then the gate as a pass of its own
-                        lib.conv_forward(dv, wt, gx, (B, Ho, Wo, Cout, Hi, Wi, Cin, KH, KW), stride=stride, pad=pad,
-                                         gather=GATHER_TRANSPOSED, residual=g_in)
-                        gated = torch.empty_like(gx)
-                        lib.act_backward(gx, gate["gate"], gated, None, B * Hi * Wi, Cin, ctx.in_gate, 1.0)
-                        gx = gated
-        elif g_in is not None:
-            gx = g_in
-        if ctx.needs_input_grad[1]:
-            # row_scale (folded FrozenBN: the layer ran with w * scale) multiplies the gradient inside the kernel's epilogue
-            if (w_sink is not None and gather == GATHER_UPSAMPLED and x.is_cuda and x.dtype == torch.bfloat16
-                    and KH == 3 and KW == 3 and pad == 1 and vv == (2 * Hi, 2 * Wi) and row_scale is None):
-                # the weight gradient through the same 4x4 / stride 2 form: D[ci][t][s][co] = sum_{y', x'} x[y', x', ci] gy[2 y' - 1 + t, 2 x' - 1 + s, co]
-                # is the ordinary weight gradient of that strided convolution (operands swapped: its input is gy, its output side x) - 16 taps per
-                # low-res pixel instead of 36, on the grouped GEMM kernels - and dW[co][kh][kw][ci] = sum_{t in T(kh), s in T(kw)} D[ci][t][s][co],
-                # T(0) = {2, 3}, T(1) = {1, 2}, T(2) = {0, 1}, added to the flat gradient when the batch has been issued
-                D = WGRADS.scratch((Cin, 4, 4, Cout), x.device)
-
-                def fold(D=D, sink=w_sink, shape=(Cout, KH, KW, Cin)):
-                    lib.upsample_taps_fold(D, sink[0].view(shape))
-                    if sink[1] is not None:
-                        sink[1]()
-
-                WGRADS.add(dv, x, D, (B, Ho, Wo, Cout, Hi, Wi, Cin, 4, 4), dict(stride=2, pad=1), fold)
-            elif w_sink is not None:
-                # the kernel ACCUMULATES (fp32 atomics): add straight into the flat gradient buffer, no temporary
-                kw, hook = dict(stride=stride, pad=pad, gather=gather, virt=vv, scale=row_scale), w_sink[1]
-                if (has_bias and ctx.needs_input_grad[2] and not bias_done and b_sink is not None and x.is_cuda
-                        and lib.conv_wgrad_takes_bias(x, dv, dims, WGRADS.active, **kw)):
-                    # the weight-gradient kernel stages every element of dv anyway: it sums the bias gradient from its dY tiles, and the
-                    # column-sum pass over the same map below is not run; both hooks fire once the job has been issued
-                    kw["dbias"], bias_done = b_sink[0], True
-                    if b_sink[1] is not None:
-                        hook = _both(w_sink[1], b_sink[1])
-                WGRADS.add(x, dv, w_sink[0], dims, kw, hook)
-            else:
-                gw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
-                lib.conv_wgrad(x, dv, gw, dims, stride=stride, pad=pad, gather=gather, virt=vv, scale=row_scale)
-        if has_bias and ctx.needs_input_grad[2] and not bias_done:
-            if b_sink is not None:
-                COLSUMS.add(dv, b_sink[0], rows, Cout, b_sink[1])
-            else:
-                gb = torch.zeros(Cout, dtype=torch.float32, device=gy.device)
-                lib.colsum(dv, gb, rows, Cout)
-        gres = (g_skip if mult is not None else dv) if (has_res and ctx.needs_input_grad[3]) else None
+            gx = _conv_dgrad(x, w, row_scale, dv, g_in, dims, stride, pad, gather, vv, ctx.in_gate, gate_src)
+        gw, gb = _conv_param_grads(x, w, row_scale, dv, dims, stride, pad, gather, vv, ctx.needs_input_grad[1], want_b and not bias_done,
+                                   w_sink, b_sink)
+        # the post-dropout skip connection gets the incoming gradient as is
+        gres = (gy if mult is not None else dv) if (has_res and ctx.needs_input_grad[3]) else None
         return gx, gw, gb, gres, None, None, None, None, None, None, None, None, None, None, None, None, None, None
+
+
+def _conv_act_backward(gy, ref, mult, act, act_scale, defer, b_sink, dims):
+    """First step of _ConvFn.backward: dropout multiplier, activation backward and, where it comes for free, the bias gradient.
+    b_sink: the bias' sink where the layer has a bias whose gradient is wanted in one, else None.  -> (dv, the gradient w.r.t. the
+    convolution's own output; whether the bias gradient has been summed into b_sink here)."""
+    lib = _lib()
+    rows, Cout = dims[0] * dims[4] * dims[5], dims[6]
+
+    def with_colsum(g, dv, m):
+        # [dropout multiplier,] activation backward and the bias gradient (column sums of dv) in ONE pass, straight into the flat
+        # gradient; False: no kernel for the shape, nothing was launched
+        done = lib.act_backward_colsum(g, ref, dv, b_sink[0], rows, Cout, act, act_scale, mult=m)
+        if done and b_sink[1] is not None:
+            b_sink[1]()
+        return done
+
+    if defer:
+        return gy, False                               # the consumer's data-gradient epilogue has applied act'(.) already
+    if mult is not None:
+        if b_sink is not None:
+            dv = torch.empty_like(gy)
+            if with_colsum(gy, dv, mult):              # (was: an ATen multiply, then the rest)
+                return dv, True
+        gy = gy * mult
+    if act == ACT_NONE and act_scale == 1.0:
+        return gy, False
+    dv = torch.empty_like(gy)
+    bias_done = b_sink is not None and with_colsum(gy, dv, None)
+    if not bias_done:
+        lib.act_backward(gy, ref, dv, None, rows, Cout, act, act_scale)
+    return dv, bias_done
+
+
+def _conv_dgrad(x, w, row_scale, dv, g_in, dims, stride, pad, gather, vv, in_gate, gate_src):
+    """Second step of _ConvFn.backward: the gradient w.r.t. the input x, with g_in (the input's second gradient, fan-out) added and
+    the backward of the producer's activation applied where the layer is that producer's gated consumer (in_gate)."""
+    lib = _lib()
+    B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW = dims
+    wt = _weight_transposed(w, row_scale, x.dtype)
+    gate = dict(gate=(x if gate_src is None else gate_src), gate_act=in_gate) if in_gate != ACT_NONE else {}
+    if (gather == GATHER_UPSAMPLED and x.is_cuda and x.dtype == torch.bfloat16 and KH == 3 and KW == 3
+            and pad == 1 and vv == (2 * Hi, 2 * Wi) and row_scale is None and (g_in is None or not gate)):
+        # one strided convolution of the gradient with the 4x4 collapse of the weights (see _upsampled_dgrad_weight)
+        gx = torch.empty_like(x)
+        lib.conv_forward(dv, _upsampled_dgrad_weight(w, x.dtype), gx, (B, Ho, Wo, Cout, Hi, Wi, Cin, 4, 4), stride=2, pad=1,
+                         residual=g_in, **gate)
+        return gx
+    if gather == GATHER_UPSAMPLED:
+        gxv = torch.empty((B, vv[0], vv[1], Cin), dtype=x.dtype, device=x.device)
+        lib.conv_forward(dv, wt, gxv, (B, Ho, Wo, Cout, vv[0], vv[1], Cin, KH, KW), stride=1, pad=pad, gather=GATHER_TRANSPOSED)
+        if gate and g_in is None:                      # the gate rides on the footprint sum
+            return _nearest_upsample_backward(gxv, Hi, Wi, gate=x, gate_act=in_gate)
+        gx = _nearest_upsample_backward(gxv, Hi, Wi)
+        if g_in is not None:
+            gx = gx + g_in
+        if gate:                                       # behind the skip gradient: a pass of its own
+            gated = torch.empty_like(gx)
+            lib.act_backward(gx, x, gated, None, B * Hi * Wi, Cin, in_gate, 1.0)
+            gx = gated
+        return gx
+    gx = torch.empty_like(x)
+    if KH == 1 and KW == 1 and stride > 1 and pad == 0 and not gate:
+        # 1x1 / stride s: only the pixels (s i, s j) get a gradient - a plain GEMM over the OUTPUT pixels, then placement
+        # (+ the skip gradient) in one pass; the transposed gather spent 3/4 of its work on zero-page products
+        q = torch.empty((B, Ho, Wo, Cin), dtype=x.dtype, device=x.device)
+        lib.conv_forward(dv, wt, q, (B, Ho, Wo, Cout, Ho, Wo, Cin, 1, 1), stride=1, pad=0, gather=GATHER_TRANSPOSED)
+        if lib.stride_place(q, g_in, gx, stride):
+            return gx
+    if lib.conv_forward(dv, wt, gx, _dgrad_dims(dims), stride=stride, pad=pad, gather=GATHER_TRANSPOSED, residual=g_in, **gate) is False:
+        # no kernel with the GELU gate for this shape: the data gradient, then the gate as a pass of its own
+        lib.conv_forward(dv, wt, gx, _dgrad_dims(dims), stride=stride, pad=pad, gather=GATHER_TRANSPOSED, residual=g_in)
+        gated = torch.empty_like(gx)
+        lib.act_backward(gx, gate["gate"], gated, None, B * Hi * Wi, Cin, in_gate, 1.0)
+        gx = gated
+    return gx
+
+
+def _conv_param_grads(x, w, row_scale, dv, dims, stride, pad, gather, vv, want_w, want_b, w_sink, b_sink):
+    """Third step of _ConvFn.backward: weight and bias gradient -> (gw, gb) as autograd gets them (None for what went into a sink).
+    want_b: the layer has a bias whose gradient is wanted and the activation pass has not summed it.  This is the one place that decides
+    who sums it then: the weight-gradient kernel, or a column-sum pass."""
+    lib = _lib()
+    B, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW = dims
+    gw = gb = None
+    if want_w:
+        # row_scale (folded FrozenBN: the layer ran with w * scale) multiplies the gradient inside the kernel's epilogue
+        if (w_sink is not None and gather == GATHER_UPSAMPLED and x.is_cuda and x.dtype == torch.bfloat16
+                and KH == 3 and KW == 3 and pad == 1 and vv == (2 * Hi, 2 * Wi) and row_scale is None):
+            # the weight gradient through the same 4x4 / stride 2 form: D[ci][t][s][co] = sum_{y', x'} x[y', x', ci] gy[2 y' - 1 + t, 2 x' - 1 + s, co]
+            # is the ordinary weight gradient of that strided convolution (operands swapped: its input is gy, its output side x) - 16 taps per
+            # low-res pixel instead of 36, on the grouped GEMM kernels - and dW[co][kh][kw][ci] = sum_{t in T(kh), s in T(kw)} D[ci][t][s][co],
+            # T(0) = {2, 3}, T(1) = {1, 2}, T(2) = {0, 1}, added to the flat gradient when the batch has been issued
+            D = WGRADS.scratch((Cin, 4, 4, Cout), x.device)
+
+            def fold(D=D, sink=w_sink, shape=(Cout, KH, KW, Cin)):
+                lib.upsample_taps_fold(D, sink[0].view(shape))
+                if sink[1] is not None:
+                    sink[1]()
+
+            WGRADS.add(dv, x, D, (B, Ho, Wo, Cout, Hi, Wi, Cin, 4, 4), dict(stride=2, pad=1), fold)
+        else:
+            kw, sink = dict(stride=stride, pad=pad, gather=gather, virt=vv, scale=row_scale), w_sink
+            if (w_sink is not None and want_b and b_sink is not None and x.is_cuda
+                    and lib.conv_wgrad_takes_bias(x, dv, dims, WGRADS.active, **kw)):
+                # the weight-gradient kernel stages every element of dv anyway: it sums the bias gradient from its dY tiles, and the
+                # column-sum pass over the same map below is not run; both hooks fire once the job has been issued
+                kw["dbias"], want_b = b_sink[0], False
+                if b_sink[1] is not None:
+                    sink = (w_sink[0], _both(w_sink[1], b_sink[1]))
+            gw = _conv_wgrad(x, dv, w, dims, kw, sink)
+    if want_b:
+        rows = B * Ho * Wo
+        if b_sink is not None:
+            COLSUMS.add(dv, b_sink[0], rows, Cout, b_sink[1])
+        else:
+            gb = torch.zeros(Cout, dtype=torch.float32, device=dv.device)
+            lib.colsum(dv, gb, rows, Cout)
+    return gw, gb
 
 
 def _nearest_upsample_backward(gv, Hi, Wi, gate=None, gate_act=ACT_NONE):
@@ -717,15 +772,10 @@ def conv2d(x, w, bias=None, *, stride=1, pad=0, act=ACT_NONE, act_scale=1.0, res
     fanout: return (y, x'), x' = x for the OTHER consumer of the input (use x' instead of x there): see _ConvFn.forward.
     defer / in_gate: a ReLU / ELU layer whose output has exactly ONE consumer (this function again, or the fan-out chain that starts
     with it) is called with defer=True and that consumer with in_gate=<the producer's activation>: the activation's backward then
-    runs in the consumer's data-gradient epilogue instead of as a pass of its own (act_gate_enabled(): both or neither)."""
+    runs in the consumer's data-gradient epilogue instead of as a pass of its own (both or neither)."""
     sinks = (_sink(w), _sink(bias) if bias is not None else None)
     return _ConvFn.apply(x, w, bias, residual, row_scale, shift, stride, pad, act, float(act_scale), upsample_to,
                          getattr(w, "_gwd_bf16", None), sinks if (sinks[0] or sinks[1]) else None, mult, bool(fanout), in_gate, defer)
-
-
-def act_gate_enabled():
-    """ReLU / ELU layers with a single consumer run their backward in that consumer's data-gradient epilogue (conv2d defer / in_gate)."""
-    return True
 
 
 def linear(x, w, bias=None, act=ACT_NONE, rows=None, residual=None, mult=None, fanout=False, defer=False, in_gate=ACT_NONE, gate_src=None):
@@ -765,6 +815,39 @@ def linear(x, w, bias=None, act=ACT_NONE, rows=None, residual=None, mult=None, f
     return y.view(*lead, n)
 
 
+def _ln_backward(gy, x, g, b, mean, rstd, gelu, sinks, g_in=None, in_gate=ACT_NONE):
+    """Backward of y = [GELU](LayerNorm(x)) over the first C = len(g) channels of rows of pitch x.shape[-1] (more channels than affine
+    entries: the rest is zero padding, _PadConvFn): gwd_layernorm_backward, with d gamma / d beta into their sinks (sinks =
+    ((dgamma, hook), (dbeta, hook))) or into fresh zeros.  g_in: a second gradient of x (fan-out), added in the kernel; in_gate = ACT_ELU:
+    x is an ELU output whose backward is applied as well.  -> (gx, what autograd gets for gamma, for beta)."""
+    lib = _lib()
+    ld = x.shape[-1]
+    C = g.shape[0] if g is not None else ld
+    rows = x.numel() // ld
+    gx = torch.empty_like(x)
+    dg = db = None
+    if sinks is not None:
+        (dg, h1), (db, h2) = sinks
+    elif g is not None:
+        dg = torch.zeros(C, dtype=torch.float32, device=x.device)
+        db = torch.zeros(C, dtype=torch.float32, device=x.device)
+    fused = lib.layernorm_backward(gy, x, g, b, mean, rstd, gx, dg, db, rows, C, gelu, ld=0 if ld == C else ld, gskip=g_in,
+                                   elu_input=in_gate == ACT_ELU)
+    if fused is False:                                 # no vector kernel for this width: the skip gradient / the gate as passes
+        if g_in is not None:
+            gx = gx + g_in
+        if in_gate != ACT_NONE:
+            gated = torch.empty_like(gx)
+            lib.act_backward(gx, x, gated, None, rows, ld, in_gate, 1.0)
+            gx = gated
+    if sinks is None:
+        return gx, dg, db
+    for h in (h1, h2):
+        if h is not None:
+            h()
+    return gx, None, None
+
+
 class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, gelu, sinks, residual, fanout=False, in_gate=ACT_NONE):
@@ -794,36 +877,11 @@ class _LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, *g_fan):
-        lib = _lib()
-        g_in = g_fan[0].contiguous() if (ctx.fan and g_fan and g_fan[0] is not None) else None
+        g_in = _fan_in(ctx, g_fan)
         x, g, b, mean, rstd = ctx.saved_tensors
-        ld = x.shape[-1]
-        C = g.shape[0] if g is not None else ld
-        rows = x.numel() // ld
         gy = gy.contiguous()
-        gx = torch.empty_like(x)
-        dg = db = None
-        direct = ctx.sinks is not None
-        if direct:
-            (dg, h1), (db, h2) = ctx.sinks
-        elif g is not None:
-            dg = torch.zeros(C, dtype=torch.float32, device=x.device)
-            db = torch.zeros(C, dtype=torch.float32, device=x.device)
-        fused = lib.layernorm_backward(gy, x, g, b, mean, rstd, gx, dg, db, rows, C, ctx.gelu, ld=0 if ld == C else ld, gskip=g_in,
-                                       elu_input=ctx.in_gate == ACT_ELU)
-        if fused is False:                                 # no vector kernel for this width: the skip gradient / the gate as passes
-            if g_in is not None:
-                gx = gx + g_in
-            if ctx.in_gate != ACT_NONE:
-                gated = torch.empty_like(gx)
-                lib.act_backward(gx, x, gated, None, rows, ld, ctx.in_gate, 1.0)
-                gx = gated
+        gx, dg, db = _ln_backward(gy, x, g, b, mean, rstd, ctx.gelu, ctx.sinks, g_in, ctx.in_gate)
         gres = gy if ctx.has_res else None                # y = LN(x) + residual: the skip gets the incoming gradient as is
-        if direct:
-            for h in (h1, h2):
-                if h is not None:
-                    h()
-            return gx, None, None, None, None, gres, None, None
         return gx, dg, db, None, None, gres, None, None
 
 
@@ -888,56 +946,14 @@ class _ConvLnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, *g_fan):
-        lib = _lib()
-        g_in = g_fan[0].contiguous() if (ctx.fan and g_fan and g_fan[0] is not None) else None
+        g_in = _fan_in(ctx, g_fan)
         x, w, z, g, b, mean, rstd = ctx.saved_tensors
         dims, pad, gelu, geom, w_sink, ln_sinks, has_res = ctx.cfg
-        B, Hi, Wi, Cin, Ho, Wo, Np, KH, KW = dims
-        N = g.shape[0]
-        rows = B * Ho * Wo
         gy = gy.contiguous()
-        # ---- LayerNorm backward (as _LayerNormFn.backward): gradient w.r.t. the convolution's output, d gamma / d beta into their sinks
-        gz = torch.empty_like(z)
-        dg = db = None
-        if ln_sinks is not None:
-            (dg, h1), (db, h2) = ln_sinks
-        else:
-            dg = torch.zeros(N, dtype=torch.float32, device=x.device)
-            db = torch.zeros(N, dtype=torch.float32, device=x.device)
-        lib.layernorm_backward(gy, z, g, b, mean, rstd, gz, dg, db, rows, N, gelu, ld=0 if Np == N else Np)
-        if ln_sinks is not None:
-            for h in (h1, h2):
-                if h is not None:
-                    h()
-        # ---- convolution backward (as _ConvFn / _PadConvFn.backward)
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            wt = _weight_transposed(w, None, x.dtype) if geom is None else _padded_weight_for(w, geom, "t", x.dtype)
-            lib.conv_forward(gz, wt, gx, (B, Ho, Wo, Np, Hi, Wi, Cin, KH, KW), stride=1, pad=pad, gather=GATHER_TRANSPOSED, residual=g_in)
-        elif g_in is not None:
-            gx = g_in
-        if ctx.needs_input_grad[1]:
-            if geom is None:
-                if w_sink is not None:
-                    WGRADS.add(x, gz, w_sink[0], dims, dict(stride=1, pad=pad), w_sink[1])
-                else:
-                    gw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
-                    lib.conv_wgrad(x, gz, gw, dims, stride=1, pad=pad)
-            else:
-                _, Cg, Cgp = geom
-                C = w.shape[-1]
-                tmp = WGRADS.scratch((Np, KH, KW, Cin), x.device)
-                fold = (N, KH * KW, C // Cg, Cg, Cgp)
-                if w_sink is not None:
-                    WGRADS.add(x, gz, tmp, dims, dict(stride=1, pad=pad), w_sink[1], unpad=(w_sink[0].view(-1),) + fold)
-                else:
-                    lib.conv_wgrad(x, gz, tmp, dims, stride=1, pad=pad)
-                    gw = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
-                    lib.unpad_add_batch([(tmp, gw.view(-1)) + fold])
+        # the gradient w.r.t. the convolution's output, d gamma / d beta; then the convolution's own backward
+        gz, dg, db = _ln_backward(gy, z, g, b, mean, rstd, gelu, ln_sinks)
+        gx, gw = _conv_backward_stride1(ctx.needs_input_grad[0], ctx.needs_input_grad[1], x, w, gz, g_in, dims, pad, geom, w_sink)
         gres = gy if has_res else None                      # y = ... + residual: the skip gets the incoming gradient as is
-        if ln_sinks is not None:
-            return gx, gw, None, None, gres, None, None, None, None, None, None
         return gx, gw, dg, db, gres, None, None, None, None, None, None
 
 
@@ -1263,6 +1279,40 @@ def psp_pools(x, pools):
     return x, [avg_pool(x, k) for k in pools]
 
 
+def _pyramid_cat_forward(x, ys):
+    """-> ([x | up(y_1) | ... | up(y_n)], cfg for _pyramid_cat_backward): see _PyramidCatFn."""
+    lib = _lib()
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    n = len(ys)
+    out = torch.empty((B, H, W, (n + 1) * C), dtype=x.dtype, device=x.device)
+    out[..., :C].copy_(x)
+    shapes = []
+    for k, y in enumerate(ys):
+        y = y.contiguous()
+        if y.shape[0] != B or y.shape[3] != C:
+            raise ValueError("pyramid_concat: branch %d has shape %r" % (k, tuple(y.shape)))
+        lib.resample_forward(y, out[..., (k + 1) * C:(k + 2) * C], B, y.shape[1], y.shape[2], H, W, C, hip.RESAMPLE_BILINEAR_AC)
+        shapes.append((y.shape[1], y.shape[2]))
+    return out, (B, H, W, C, shapes)
+
+
+def _pyramid_cat_backward(cfg, g):
+    """g, the gradient of _pyramid_cat_forward's result -> [the gradient of x (a view of g), of y_1, ..., of y_n]."""
+    lib = _lib()
+    B, H, W, C, shapes = cfg
+    g = g.contiguous()
+    grads = [g[..., :C]]
+    for k, (h, w) in enumerate(shapes):
+        gk = g[..., (k + 1) * C:(k + 2) * C]
+        gy = torch.empty((B, h, w, C), dtype=g.dtype, device=g.device)
+        tmp = torch.empty(lib.workspace_bytes(hip.WS_RESAMPLE_BWD, B, H, w, C) // 4, dtype=torch.float32, device=g.device)
+        if not lib.resample_backward_sep(gk, tmp, gy, B, h, w, H, W, C, hip.RESAMPLE_BILINEAR_AC):
+            lib.resample_backward(gk.contiguous(), gy, B, h, w, H, W, C, hip.RESAMPLE_BILINEAR_AC)
+        grads.append(gy)
+    return grads
+
+
 class _PyramidCatFn(torch.autograd.Function):
     """cat([x, up(y_1), ..., up(y_n)], channels) with up = bilinear(align_corners) to x's size (the PSP tail of
     points_sample.py:114-122) WITHOUT the concat pass: the up-sampling kernels write their channel slice of the result directly
@@ -1271,36 +1321,12 @@ class _PyramidCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *ys):
-        lib = _lib()
-        x = x.contiguous()
-        B, H, W, C = x.shape
-        n = len(ys)
-        out = torch.empty((B, H, W, (n + 1) * C), dtype=x.dtype, device=x.device)
-        out[..., :C].copy_(x)
-        shapes = []
-        for k, y in enumerate(ys):
-            y = y.contiguous()
-            if y.shape[0] != B or y.shape[3] != C:
-                raise ValueError("pyramid_concat: branch %d has shape %r" % (k, tuple(y.shape)))
-            lib.resample_forward(y, out[..., (k + 1) * C:(k + 2) * C], B, y.shape[1], y.shape[2], H, W, C, hip.RESAMPLE_BILINEAR_AC)
-            shapes.append((y.shape[1], y.shape[2]))
-        ctx.cfg = (B, H, W, C, shapes)
+        out, ctx.cfg = _pyramid_cat_forward(x, ys)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib()
-        B, H, W, C, shapes = ctx.cfg
-        g = g.contiguous()
-        grads = [g[..., :C]]
-        for k, (h, w) in enumerate(shapes):
-            gk = g[..., (k + 1) * C:(k + 2) * C]
-            gy = torch.empty((B, h, w, C), dtype=g.dtype, device=g.device)
-            tmp = torch.empty(lib.workspace_bytes(hip.WS_RESAMPLE_BWD, B, H, w, C) // 4, dtype=torch.float32, device=g.device)
-            if not lib.resample_backward_sep(gk, tmp, gy, B, h, w, H, W, C, hip.RESAMPLE_BILINEAR_AC):
-                lib.resample_backward(gk.contiguous(), gy, B, h, w, H, W, C, hip.RESAMPLE_BILINEAR_AC)
-            grads.append(gy)
-        return tuple(grads)
+        return tuple(_pyramid_cat_backward(ctx.cfg, g))
 
 
 def pyramid_concat(x, ys):
@@ -1313,10 +1339,6 @@ def pyramid_concat(x, ys):
 
 PYRAMID_TAIL_LOWRES = True       # PyramidLayer's last ConvLn: convolve the coarse PSP branches at their own resolution (pyramid_tail)
 PYRAMID_TAIL_NLOW = 3            # how many of the branches (coarsest first) go that way; the rest stay in the high-resolution concat
-
-
-class _Ctx:
-    """Stands in for an autograd context where a Function's forward / backward pair is reused inside another Function."""
 
 
 class _PyramidTailFn(torch.autograd.Function):
@@ -1339,8 +1361,7 @@ class _PyramidTailFn(torch.autograd.Function):
             raise ValueError("pyramid_tail: weight %r does not fit %d branches of %d channels" % (tuple(w.shape), nbr, C2))
         dt = x.dtype
         lows = [y.contiguous() for y in ys[:nlow]]
-        cctx = _Ctx()
-        cat = _PyramidCatFn.forward(cctx, x, *ys[nlow:]) if nlow < nbr else x.contiguous()
+        cat, cat_cfg = _pyramid_cat_forward(x, ys[nlow:]) if nlow < nbr else (x.contiguous(), None)
         Chi = cat.shape[-1]
         w_hi = derived_weight(w, ("pyr_tail_hi", nlow), lambda: torch.cat([w.detach()[..., :C2], w.detach()[..., (1 + nlow) * C2:]], dim=-1))
         w_lo = [derived_weight(w, ("pyr_tail_lo", k), lambda k=k: w.detach()[..., (k + 1) * C2:(k + 2) * C2].permute(1, 2, 0, 3)
@@ -1364,43 +1385,27 @@ class _PyramidTailFn(torch.autograd.Function):
             raise ValueError("pyramid_tail: no kernel for N = %d with branches %r" % (N, [tuple(y.shape[1:3]) for y in lows]))
         if need_grad:
             ctx.save_for_backward(cat, w, z, g, b, mean, rstd, *lows)
-        ctx.cfg = (dims, bool(gelu), nlow, nbr, C2, w_sink, ln_sinks, cctx, w_hi, w_lo)
+        ctx.cfg = (dims, bool(gelu), nlow, nbr, C2, w_sink, ln_sinks, cat_cfg, w_hi, w_lo)
         return out
 
     @staticmethod
     def backward(ctx, gy):
         lib = _lib()
         cat, w, z, g, b, mean, rstd, *lows = ctx.saved_tensors
-        dims, gelu, nlow, nbr, C2, w_sink, ln_sinks, cctx, w_hi, w_lo = ctx.cfg
+        dims, gelu, nlow, nbr, C2, w_sink, ln_sinks, cat_cfg, w_hi, w_lo = ctx.cfg
         B, H, W, Chi, _, _, N, _, _ = dims
         dt = cat.dtype
-        rows = B * H * W
-        gz = torch.empty_like(z)
-        dg = db = None
-        if ln_sinks is not None:
-            (dg, h1), (db, h2) = ln_sinks
-        else:
-            dg = torch.zeros(N, dtype=torch.float32, device=z.device)
-            db = torch.zeros(N, dtype=torch.float32, device=z.device)
-        lib.layernorm_backward(gy.contiguous(), z, g, b, mean, rstd, gz, dg, db, rows, N, gelu)
-        if ln_sinks is not None:
-            for h in (h1, h2):
-                if h is not None:
-                    h()
+        gz, dg, db = _ln_backward(gy.contiguous(), z, g, b, mean, rstd, gelu, ln_sinks)
         # ---- high-resolution part: data gradient of [x | the remaining branches], then the concat's own backward
-        g_cat = torch.empty_like(cat)
-        lib.conv_forward(gz, _weight_transposed(w_hi, None, dt), g_cat, (B, H, W, N, H, W, Chi, 3, 3), stride=1, pad=1, gather=GATHER_TRANSPOSED)
-        g_high = list(_PyramidCatFn.backward(cctx, g_cat)) if nlow < nbr else [g_cat]
+        g_cat = _dgrad_stride1(gz, _weight_transposed(w_hi, None, dt), cat, dims, 1)
+        g_high = _pyramid_cat_backward(cat_cfg, g_cat) if nlow < nbr else [g_cat]
         # ---- low-resolution part: the gradients of the product maps, then the 1x1 data gradients
         Gs = [torch.empty((B, y.shape[1], y.shape[2], 9, N), dtype=dt, device=z.device) for y in lows]
         lib.pyr_tail_backward(gz, Gs)
-        g_low = []
-        for y, G, wl in zip(lows, Gs, w_lo):
-            h, wd = y.shape[1], y.shape[2]
-            gyk = torch.empty_like(y)
-            lib.conv_forward(G.view(B, h, wd, 9 * N), _weight_transposed(wl, None, dt), gyk, (B, h, wd, 9 * N, h, wd, C2, 1, 1), stride=1, pad=0,
-                             gather=GATHER_TRANSPOSED)
-            g_low.append(gyk)
+        # per branch: (y_k, the gradient of Z_k as one map of 9 N channels, the dims of the 1x1 convolution y_k -> Z_k)
+        low = [(y, G.view(B, y.shape[1], y.shape[2], 9 * N), (B, y.shape[1], y.shape[2], C2, y.shape[1], y.shape[2], 9 * N, 1, 1))
+               for y, G in zip(lows, Gs)]
+        g_low = [_dgrad_stride1(G, _weight_transposed(wl, None, dt), y, d, 0) for (y, G, d), wl in zip(low, w_lo)]
         # ---- weight gradients: each part in its own shape, folded into the parameter's layout once all have been issued
         gw = None
         if ctx.needs_input_grad[1]:
@@ -1416,12 +1421,9 @@ class _PyramidTailFn(torch.autograd.Function):
                     hook()
 
             WGRADS.add(cat, gz, d_hi, dims, dict(stride=1, pad=1))
-            for i, (y, G, d) in enumerate(zip(lows, Gs, d_lo)):
-                h, wd = y.shape[1], y.shape[2]
-                WGRADS.add(y, G.view(B, h, wd, 9 * N), d, (B, h, wd, C2, h, wd, 9 * N, 1, 1), dict(stride=1, pad=0),
-                           fold if i == len(lows) - 1 else None)
-        grads = g_high[:1] + [gw] + ([None, None] if ln_sinks is not None else [dg, db]) + [None] * 4 + g_low + g_high[1:]
-        return tuple(grads)
+            for i, ((y, G, d), dw) in enumerate(zip(low, d_lo)):
+                WGRADS.add(y, G, dw, d, dict(stride=1, pad=0), fold if i == len(lows) - 1 else None)
+        return tuple(g_high[:1] + [gw, dg, db] + [None] * 4 + g_low + g_high[1:])
 
 
 def pyramid_tail_supported(x, ys, w):
