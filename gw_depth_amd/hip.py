@@ -38,6 +38,7 @@ ENTRY_POINTS = [
     "gwd_dense_postprocess_resized",
     "gwd_resample_u8_pass_batch", "gwd_gather2d_batch", "gwd_color_adjust_batch",
     "gwd_pyr_tail_forward", "gwd_pyr_tail_backward", "gwd_pyr_tail_fold_wgrad",
+    "gwd_widen_u16_batch",
 ]
 
 
@@ -103,6 +104,12 @@ class ImageJob(ctypes.Structure):
                 ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
 
 
+class WidenJob(ctypes.Structure):
+    """gwd_widen_job (include/gwdepth.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n", ctypes.c_int64)]
+
+
+WIDEN_BATCH = 16          # gwd_widen_u16_batch jobs: the depth planes of one batch
 AUGMENT_BATCH = 16        # frames per grouped augmentation launch
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
 COLOR_ADJUST, COLOR_SUMS = 0, 1
@@ -279,6 +286,7 @@ class HipLibrary:
         L.gwd_pyr_tail_forward.argtypes = [vp, pvp, pi32, pi32, i32] + [vp] * 6 + [i32] * 6 + [vp]
         L.gwd_pyr_tail_backward.argtypes = [vp, pvp, pi32, pi32, i32] + [i32] * 5 + [vp]
         L.gwd_pyr_tail_fold_wgrad.argtypes = [vp, pvp, i32, vp, i32, i32, i32, vp]
+        L.gwd_widen_u16_batch.argtypes = [ctypes.POINTER(WidenJob), i32, vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -585,6 +593,24 @@ class HipLibrary:
         f3 = ctypes.c_float * 3
         self._check(self.lib.gwd_collate(jobs, len(samples), H, W, f3(*mean), f3(*std), _ptr(images), _ptr(mask), _ptr(depth),
                                          _ptr(seg), dtype_code(images), self._stream(*ts)), "gwd_collate")
+
+    def widen_u16_batch(self, jobs):
+        """gwd_widen_u16_batch.  jobs: up to WIDEN_BATCH pairs (src, dst): src the 2 * n bytes of a little-endian unsigned 16-bit plane
+        (a uint8 view of a record, or a 2-byte tensor of n elements), dst a contiguous int32 tensor of n elements."""
+        if not 0 < len(jobs) <= WIDEN_BATCH:
+            raise ValueError("1..%d planes per call" % WIDEN_BATCH)
+        recs = (WidenJob * len(jobs))()
+        ts = []
+        for r, (src, dst) in zip(recs, jobs):
+            if dst.dtype != torch.int32 or src.element_size() not in (1, 2) or src.numel() * src.element_size() != 2 * dst.numel():
+                raise ValueError("widen_u16_batch: 2 * n source bytes for an int32 plane of n elements expected")
+            if not (src.is_contiguous() and dst.is_contiguous()):
+                raise ValueError("kernel operand must be contiguous")
+            # an empty view has no data_ptr(): its place in the storage stands in (the entry point skips n == 0 and reads nothing)
+            r.src, r.dst = (t.data_ptr() or t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size() for t in (src, dst))
+            r.n = dst.numel()
+            ts += [src, dst]
+        self._check(self.lib.gwd_widen_u16_batch(recs, len(jobs), self._stream(*ts)), "gwd_widen_u16_batch")
 
     @staticmethod
     def _tok(t):

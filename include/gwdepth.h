@@ -761,6 +761,19 @@ typedef struct {
 int gwd_collate(const gwd_image_job *jobs, int32_t n, int32_t H, int32_t W, const float *mean, const float *std,
                 void *images, uint8_t *mask, float *depth, int64_t *seg, int32_t dtype, void *stream);
 
+/* Widens up to GWD_WIDEN_BATCH planes of unsigned 16-bit values (depth in millimetres as the PNG decoder produced it, kept in a
+ * sample's record: gw_depth_amd/dataset.py) to the int32 planes gwd_gather2d_batch / gwd_collate take, in ONE launch: dst[k] = src[k]
+ * zero-extended (65535 stays 65535) for k < n.  `jobs` is a HOST array; the records travel in the kernel arguments (nothing is
+ * uploaded, nothing must outlive the call).  src needs 2-byte alignment only, dst 4-byte (-3 otherwise); jobs with n == 0 are
+ * skipped; a null pointer, n < 0 or n_jobs outside 1..GWD_WIDEN_BATCH returns -1.  No allocation, no synchronisation, no atomics.  */
+#define GWD_WIDEN_BATCH 16
+typedef struct {
+    const uint16_t *src;
+    int32_t *dst;
+    int64_t n;
+} gwd_widen_job;
+int gwd_widen_u16_batch(const gwd_widen_job *jobs, int32_t n_jobs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
