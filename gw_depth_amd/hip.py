@@ -39,6 +39,7 @@ ENTRY_POINTS = [
     "gwd_resample_u8_pass_batch", "gwd_gather2d_batch", "gwd_color_adjust_batch",
     "gwd_pyr_tail_forward", "gwd_pyr_tail_backward", "gwd_pyr_tail_fold_wgrad",
     "gwd_widen_u16_batch",
+    "gwd_line_nms",
 ]
 
 
@@ -287,6 +288,7 @@ class HipLibrary:
         L.gwd_pyr_tail_backward.argtypes = [vp, pvp, pi32, pi32, i32] + [i32] * 5 + [vp]
         L.gwd_pyr_tail_fold_wgrad.argtypes = [vp, pvp, i32, vp, i32, i32, i32, vp]
         L.gwd_widen_u16_batch.argtypes = [ctypes.POINTER(WidenJob), i32, vp]
+        L.gwd_line_nms.argtypes = [vp] * 4 + [ctypes.c_double, f32] + [vp] * 4 + [i32] * 4 + [vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -571,6 +573,26 @@ class HipLibrary:
             _ptr(logits), _ptr(lines), _ptr(sizes), _ptr(gt), _ptr(gt_count), nms, T, sap, S, _ptr(flag), _ptr(kept_lines), _ptr(score),
             _ptr(gt_seen), B, Q, ld, G, cap, int(slot),
             self._stream(logits, lines, sizes, gt, gt_count, flag, kept_lines, score, gt_seen)), "gwd_line_score")
+
+    def line_nms(self, logits, lines, sizes, order, threshold, min_score, nms_lines, nms_scores, nms_ids, nms_count, twin):
+        """gwd_line_nms: logits (B+twin,Q,2) / lines (B+twin,Q,ld) fp32, sizes (B,2) int32, order (B+twin,Q) int32 or None; outputs
+        nms_lines (B,C,4) f64, nms_scores (B,C) fp32, nms_ids (B,C) / nms_count (B,) int32 with C = Q, or 2 Q with twin = B.
+        min_score None = no floor.  At most 1024 candidates per image."""
+        for t, dt in ((logits, torch.float32), (lines, torch.float32), (sizes, torch.int32), (order, torch.int32),
+                      (nms_lines, torch.float64), (nms_scores, torch.float32), (nms_ids, torch.int32), (nms_count, torch.int32)):
+            if t is not None and t.dtype != dt:
+                raise TypeError("gwd_line_nms: expected %s, got %s" % (dt, t.dtype))
+        Bs, Q, ld = lines.shape
+        twin = int(twin)
+        B, C = Bs - twin, Q * (2 if twin else 1)
+        if twin < 0 or B <= 0 or (twin and twin != B) or tuple(logits.shape) != (Bs, Q, 2) or tuple(sizes.shape) != (B, 2) \
+                or (order is not None and tuple(order.shape) != (Bs, Q)) or tuple(nms_lines.shape) != (B, C, 4) \
+                or tuple(nms_scores.shape) != (B, C) or tuple(nms_ids.shape) != (B, C) or nms_count.numel() != B:
+            raise ValueError("gwd_line_nms: operand sizes do not match (B, Q, ld, twin) = %r" % ((B, Q, ld, twin),))
+        self._check(self.lib.gwd_line_nms(
+            _ptr(logits), _ptr(lines), _ptr(sizes), _ptr(order), float(threshold), float("nan") if min_score is None else float(min_score),
+            _ptr(nms_lines), _ptr(nms_scores), _ptr(nms_ids), _ptr(nms_count), B, Q, ld, twin,
+            self._stream(logits, lines, sizes, order, nms_lines, nms_scores, nms_ids, nms_count)), "gwd_line_nms")
 
     def plane_loss_forward(self, depth, valid, tri, n_planes, P, H, W, min_area, workspace, stats, loss):
         self._check(self.lib.gwd_plane_loss_forward(_ptr(depth), _ptr(valid), _ptr(tri), _ptr(n_planes), P, H, W, min_area,

@@ -7,8 +7,9 @@ launches every kernel from Python and ends at raw tensors.  An InferenceSession
   copy is made when its weight is first seen (the first call) and stays; refresh() rewrites all of them in place with one launch;
 * replays a captured HIP graph per input signature (B, H, W): forward and post-processing, on one private stream, out of one
   memory pool, least recently used signature dropped beyond engine.MAX_GRAPHS;
-* finishes on the device: the un-padded sizes from the pad mask, the dense post-processing (gwd_dense_postprocess) and
-  the line post-processing with a ranking (gwd_line_postprocess), both inside the captured graph, no host sync anywhere.
+* finishes on the device: the un-padded sizes from the pad mask, the dense post-processing (gwd_dense_postprocess), the line
+  post-processing with a ranking (gwd_line_postprocess) and - where asked for (line_nms=) - L-CNN's line NMS over the queries
+  (gwd_line_nms), all inside the captured graph, no host sync anywhere.
 """
 import contextlib
 import gc
@@ -22,6 +23,7 @@ from . import data, engine, hip, ops
 from .model import NestedTensor, nested_tensor_from_tensor_list
 
 RESULT_KEYS = ("depth", "depth_mm", "labels", "scores", "lines", "order", "count", "sizes")
+NMS_KEYS = ("nms_lines", "nms_scores", "nms_ids", "nms_count")          # added to a result by a session built with line_nms=
 
 
 def _count_memsets_in(fn):
@@ -63,12 +65,28 @@ class InferenceSession:
     sess.predict_frames(frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False): decoded uint8 (h,w,3) camera
     frames in, the same results at every frame's OWN size out (see the method).
 
+    LINE NMS.  line_nms=None (the default): the line results are the raw queries, as above.  line_nms=t (the reference's consumers
+    use 0.010 and 0.015 of the image diagonal): predict / predict_frames also return NMS_KEYS - nms_lines (B,C,4) float64
+    (x1, y1, x2, y2) pixels at the size `lines` are scaled to, nms_scores (B,C), nms_ids (B,C) int32, nms_count (B,) int32:
+    row r of an image is its r-th kept (clipped) line, rows from nms_count on hold 0 / 0 / -1 (ops.line_nms).  The queries are
+    taken by score (line_nms_order="score", the ranking `order`) or in query order as the reference's script takes them
+    ("query"); line_nms_min_score=s lets only queries with score > s take part.  C = Q; with predict_frames(ensemble=True)
+    the mirrored twin's queries, mirrored back, take part as well: C = 2 Q and ids >= Q name the twin's queries.
+
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
 
-    def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6):
+    def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6,
+                 line_nms=None, line_nms_order="score", line_nms_min_score=None):
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
+        if line_nms_order not in ("score", "query"):
+            raise ValueError("line_nms_order must be 'score' or 'query', got %r" % (line_nms_order,))
+        if line_nms is not None and not float(line_nms) >= 0.0:
+            raise ValueError("line_nms must be None or a fraction of the image diagonal >= 0, got %r" % (line_nms,))
+        self.line_nms = None if line_nms is None else float(line_nms)
+        self.line_nms_order = line_nms_order
+        self.line_nms_min_score = None if line_nms_min_score is None else float(line_nms_min_score)
         self.model = model
         self.compute_dtype = compute_dtype
         self.use_graph = bool(graph)
@@ -132,20 +150,29 @@ class InferenceSession:
                 weights.end_pass()
             model.compute_dtype = keep
 
-    def _post(self, out, mask, target):
+    def _post(self, out, mask, target, twin=0):
         """Device post-processing of one forward.  target (B,2) int32: the size the lines are scaled to, rows < 0 = the
-        un-padded input size."""
+        un-padded input size.  twin (line NMS only): images twin .. 2 twin - 1 are the mirrored copies of the first twin images."""
         with torch.no_grad():
             sizes = torch.stack([(~mask[:, :, 0]).sum(1, dtype=torch.int32), (~mask[:, 0, :]).sum(1, dtype=torch.int32)], dim=1)
             depth, mm, labels = ops.dense_postprocess(out["pred_depth"][-1], out["pred_seg"], sizes, self.min_depth, self.max_depth)
             lsz = torch.where(target >= 0, target, sizes)
-            scores, lines, order, count = ops.line_postprocess(out["pred_logits"], out["pred_lines"], lsz, self.score_thresh)
-        return {"depth": depth, "depth_mm": mm, "labels": labels, "scores": scores, "lines": lines, "order": order,
-                "count": count, "sizes": sizes}
+            raw_logits, raw_lines = out["pred_logits"], out["pred_lines"]
+            if self.line_nms is not None:                  # two consumers: widen the bf16 outputs once, not once per consumer
+                raw_logits, raw_lines = raw_logits.float().contiguous(), raw_lines.float().contiguous()
+            scores, lines, order, count = ops.line_postprocess(raw_logits, raw_lines, lsz, self.score_thresh)
+            res = {"depth": depth, "depth_mm": mm, "labels": labels, "scores": scores, "lines": lines, "order": order,
+                   "count": count, "sizes": sizes}
+            if self.line_nms is not None:
+                nms = ops.line_nms(raw_logits, raw_lines, lsz[:lsz.shape[0] - twin], self.line_nms,
+                                   order=order if self.line_nms_order == "score" else None, min_score=self.line_nms_min_score,
+                                   twin=twin)
+                res.update(zip(NMS_KEYS, nms))
+        return res
 
     def _pass(self, st):
         out = self._forward(st["images"], st["mask"])
-        return out, self._post(out, st["mask"], st["target"])
+        return out, self._post(out, st["mask"], st["target"], st["twin"])
 
     # ------------------------------------------------------------------ graphs
     def _graph_stream(self):
@@ -171,8 +198,8 @@ class InferenceSession:
     def _count_memsets(self, st):
         return _count_memsets_in(lambda: self._pass(st))
 
-    def _graph_entry(self, images, mask):
-        key = tuple(int(images.shape[i]) for i in (0, 2, 3))
+    def _graph_entry(self, images, mask, twin=0):
+        key = tuple(int(images.shape[i]) for i in (0, 2, 3)) + (("twin",) if twin else ())
         ent = self._graphs.get(key)
         if ent is not None:
             self._graphs.move_to_end(key)
@@ -180,7 +207,7 @@ class InferenceSession:
         while len(self._graphs) >= engine.MAX_GRAPHS:      # bounded cache; the executables go, the shared pool keeps the memory
             self._graphs.popitem(last=False)
         st = {"images": images.clone(), "mask": mask.clone(),
-              "target": torch.full((key[0], 2), -1, dtype=torch.int32, device=images.device)}
+              "target": torch.full((key[0], 2), -1, dtype=torch.int32, device=images.device), "twin": twin}
         with self._on_stream():
             self._pass(st)                                 # allocator, lazily built caches, the frozen weight copies
             memsets = self._count_memsets(st)              # second warm-up pass, audited
@@ -216,7 +243,8 @@ class InferenceSession:
 
     @property
     def graphs(self):
-        """{(B, H, W): {"captured": bool, "reason": why not}} for every signature in the cache, oldest first."""
+        """{(B, H, W): {"captured": bool, "reason": why not}} for every signature in the cache, oldest first (a session with
+        line_nms keeps the ensemble passes of predict_frames under (2B, H, W, "twin"): their NMS pairs the images up)."""
         return OrderedDict((k, {"captured": e["graph"] is not None, "reason": e.get("reason")}) for k, e in self._graphs.items())
 
     # ------------------------------------------------------------------ calls
@@ -237,12 +265,12 @@ class InferenceSession:
             raise ValueError("target_sizes must be (B, 2) = (h, w) per image, got %s" % (tuple(t.shape),))
         return t
 
-    def _run(self, samples, target_sizes, want_post, taps=None):
+    def _run(self, samples, target_sizes, want_post, taps=None, twin=0):
         images, mask = self._decompose(samples)
         B = images.shape[0]
         target = self._target(target_sizes, B, images.device)
         if self.use_graph and images.is_cuda and taps is None:
-            ent = self._graph_entry(images, mask)
+            ent = self._graph_entry(images, mask, twin)
             if ent["graph"] is not None:
                 st = ent["static"]
                 with self._on_stream():
@@ -260,7 +288,7 @@ class InferenceSession:
             if want_post:
                 if target is None:
                     target = torch.full((B, 2), -1, dtype=torch.int32, device=images.device)
-                post = self._post(out, mask, target)
+                post = self._post(out, mask, target, twin)
         return out, post
 
     def __call__(self, samples, reflc_points=None, reflc_mat=None, img_name=None, taps=None):
@@ -270,8 +298,9 @@ class InferenceSession:
     forward = __call__
 
     def predict(self, samples, target_sizes=None, copy=False):
-        """Post-processed results (RESULT_KEYS).  target_sizes (B,2) = (h, w): scale the lines to another size than the
-        un-padded input (the reference passes orig_size for evaluation).  copy=False: see LIFETIME OF OUTPUTS."""
+        """Post-processed results (RESULT_KEYS, and NMS_KEYS from a session with line_nms).  target_sizes (B,2) = (h, w): scale
+        the lines to another size than the un-padded input (the reference passes orig_size for evaluation).  copy=False: see
+        LIFETIME OF OUTPUTS."""
         res = self._run(samples, target_sizes, True)[1]
         if copy:
             res = {k: v.clone() for k, v in res.items()}
@@ -300,6 +329,9 @@ class InferenceSession:
         ensemble=True: the prediction of the mirrored frame, mirrored back, is averaged in (depth: mean; logits: sum) - the
         mirrored copies ride in the same resize launches and the same forward.
 
+        A session with line_nms adds NMS_KEYS in frame pixels; with ensemble=True the mirrored frames' queries, mirrored back,
+        are candidates too (C = 2 Q rows per frame).  Without line_nms the twin's lines stay unused.
+
         -> RESULT_KEYS + "net_sizes": depth / depth_mm / labels (B, Fh, Fw) with (Fh, Fw) the largest frame of the call (outside
         a frame 0 / 0 / 255), sizes (B,2) the FRAME sizes, net_sizes (B,2) the un-padded network sizes, scores / lines / order /
         count as predict() gives them for the B frames, lines in frame pixels.  The dense results, sizes and net_sizes are fresh
@@ -326,12 +358,13 @@ class InferenceSession:
                                                     carry=np.asarray([frame_sizes, frame_sizes, net_sizes], dtype=np.int32))
         batch = data.device_collate([o[:3] for o in out], device=dev, dtype=self.compute_dtype, pad_to=pad_to)
         fsz, nsz = table[0], table[2]                      # the lines of all 2B images are scaled to their frame's size
-        raw, post = self._run(NestedTensor(batch["images"], batch["pad_mask"]), table[:2].view(2 * B, 2) if ensemble else fsz, True)
+        raw, post = self._run(NestedTensor(batch["images"], batch["pad_mask"]), table[:2].view(2 * B, 2) if ensemble else fsz, True,
+                              twin=B if ensemble and self.line_nms is not None else 0)
         with torch.no_grad(), self._on_stream():
             depth, mm, labels = ops.dense_postprocess_resized(
                 raw["pred_depth"][-1], raw["pred_seg"], nsz, fsz, (max(s[0] for s in frame_sizes), max(s[1] for s in frame_sizes)),
                 self.min_depth, self.max_depth, twin=B if ensemble else 0)
         res = {"depth": depth, "depth_mm": mm, "labels": labels, "sizes": fsz, "net_sizes": nsz}
-        for k in ("scores", "lines", "order", "count"):
+        for k in ("scores", "lines", "order", "count") + (NMS_KEYS if self.line_nms is not None else ()):
             res[k] = post[k][:B].clone() if copy else post[k][:B]
         return res

@@ -2138,3 +2138,29 @@ def line_postprocess(logits, lines, sizes, thresh=0.6):
     count = torch.empty((B,), dtype=torch.int32, device=dev)
     _lib().line_postprocess(logits, lines, sizes, scores, lines_px, order, count, B, Q, ld, thresh)
     return scores, lines_px, order, count
+
+
+def line_nms(logits, lines, sizes, threshold, order=None, min_score=None, twin=0):
+    """L-CNN's line NMS over the queries of every image (gwd_line_nms; the reference's postprocess at tol = 0, do_clip = False):
+    logits (B+twin,Q,2), lines (B+twin,Q,4|6), sizes (B,2) int32 (h, w) the lines are scaled to, threshold a fraction of that
+    size's diagonal (the reference uses 0.010 and 0.015).  order None: the queries are taken in query order, as the reference
+    takes them; order (B+twin,Q) int32: in that order (line_postprocess's `order`: score descending).  min_score: only queries
+    with score > min_score take part.  twin = B: image b + B is the prediction for the mirrored image b, and its queries, mirrored
+    back, are candidates of image b too (appended in query order, merged by score under an order).
+    -> nms_lines (B,C,4) float64 (x1, y1, x2, y2) pixels, nms_scores (B,C), nms_ids (B,C) int32 (query index, + Q for the twin's),
+    nms_count (B,) int32, with C = Q or 2 Q: row r of an image is its r-th kept line, rows from nms_count on hold 0 / 0 / -1."""
+    Bs, Q, ld = lines.shape
+    twin = int(twin)
+    B = Bs - twin
+    if twin < 0 or B <= 0 or (twin and twin != B):
+        raise ValueError("twin must be 0 or half of the %d images, got %d" % (Bs, twin))
+    logits, lines = logits.float().contiguous(), lines.float().contiguous()
+    if order is not None:
+        order = order.contiguous()
+    dev, C = logits.device, Q * (2 if twin else 1)
+    nms_lines = torch.empty((B, C, 4), dtype=torch.float64, device=dev)
+    nms_scores = torch.empty((B, C), dtype=torch.float32, device=dev)
+    nms_ids = torch.empty((B, C), dtype=torch.int32, device=dev)
+    nms_count = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib().line_nms(logits, lines, sizes, order, threshold, min_score, nms_lines, nms_scores, nms_ids, nms_count, twin)
+    return nms_lines, nms_scores, nms_ids, nms_count

@@ -761,6 +761,30 @@ typedef struct {
 int gwd_collate(const gwd_image_job *jobs, int32_t n, int32_t H, int32_t W, const float *mean, const float *std,
                 void *images, uint8_t *mask, float *depth, int64_t *seg, int32_t dtype, void *stream);
 
+/* L-CNN's line NMS over the detector's queries (postprocess, evaluation/eval_post_online.py:44-91 of the reference, at tol = 0 and
+ * do_clip = False), one workgroup per image (csrc/linenms.hip; the scalar geometry is csrc/linescore.h, f64, no contraction): the
+ * suppressed, clipped and compacted detections of every image, in one launch, without atomics or a memset.
+ *   logits [B + twin][Q][2] fp32, lines [B + twin][Q][ld] fp32 (ld 4 or 6, x before y), sizes [B][2] int32 (h, w): the lines are
+ *   scaled to this size in fp32 and the threshold is t * sqrt(h^2 + w^2) of it; t (a fraction of the diagonal, >= 0) is a HOST value.
+ * Candidates of image b, from its Q queries: score = softmax probability of class 0 (gwd_line_postprocess's, bit for bit); the list
+ *   is cut at the first i > 0 whose ld values all equal query 0's (eval_post_online.py:127-131); with min_score a number only
+ *   score > min_score enters (a NaN score never does), min_score NaN = no floor.
+ *   order NULL: query order, as the reference passes them.  order [B + twin][Q] int32: place k of image b holds the query taken
+ *   k-th (gwd_line_postprocess's `order` gives score descending, ties by lower index); entries outside [0, Q) are skipped.
+ *   twin = B: image b + twin is the prediction for the mirrored image b; its surviving queries are candidates of image b too, mirrored
+ *   back by hflip_lines' rule (end points swapped, x -> w - x in fp32 on the pixel values).  With order NULL they follow the
+ *   image's own; with an order the two lists are merged by score (a NaN above every number), the image's own first on ties, equal
+ *   scores of one list by place.  twin = 0: none.
+ * Outputs, C = Q (twin = 0) or 2 Q rows per image, every element written; row r is the r-th kept line in candidate order:
+ *   nms_lines [B][C][4] f64 = (x1, y1, x2, y2) in pixels, clipped to the part no earlier kept line covers; nms_scores [B][C] fp32;
+ *   nms_ids [B][C] int32 = the query index, + Q for a query of the twin; nms_count [B] int32 = kept lines; rows from nms_count on
+ *   hold zeros / 0 / -1.
+ * -1 on bad arguments (a NULL other than order, ld not 4 or 6, twin not 0 or B, t negative or NaN), -2 when an image has more than
+ * 1024 candidates (Q > 1024, or 2 Q > 1024 with a twin); nothing is launched then.                                            */
+int gwd_line_nms(const float *logits, const float *lines, const int32_t *sizes, const int32_t *order, double t, float min_score,
+                 double *nms_lines, float *nms_scores, int32_t *nms_ids, int32_t *nms_count, int32_t B, int32_t Q, int32_t ld,
+                 int32_t twin, void *stream);
+
 /* Widens up to GWD_WIDEN_BATCH planes of unsigned 16-bit values (depth in millimetres as the PNG decoder produced it, kept in a
  * sample's record: gw_depth_amd/dataset.py) to the int32 planes gwd_gather2d_batch / gwd_collate take, in ONE launch: dst[k] = src[k]
  * zero-extended (65535 stays 65535) for k < n.  `jobs` is a HOST array; the records travel in the kernel arguments (nothing is
