@@ -6,13 +6,11 @@
 // workspace; eval_finalize_kernel folds them in a fixed order (bit-reproducible), turns the sums into the measures of
 // each image and adds them to the caller's running totals in image order, like the reference's loop does.
 #include "common.h"
+#include "evalterms.h"
 
 namespace {
 
 constexpr int NSUM = GWD_EVAL_NSUM;   // n, d1, d2, d3, sum sq, sum abs_rel, sum sq_rel, sum err, sum err^2, sum |log10|
-
-__device__ __forceinline__ float log_rn(float v) { return (float)log((double)v); }        // = correctly rounded logf
-__device__ __forceinline__ float log10_rn(float v) { return (float)log10((double)v); }
 
 template <typename TD, typename TS>
 __global__ __launch_bounds__(256) void eval_partial_kernel(const TD *__restrict__ pred, const float *__restrict__ gt,
@@ -28,25 +26,12 @@ __global__ __launch_bounds__(256) void eval_partial_kernel(const TD *__restrict_
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < HW; i += (int64_t)nb * 256) {
         if (pred) {
             const float g = gt[b * HW + i];
-            float p = to_f32(pred[b * HW + i]);
-            // engine_glassrgbd.py:249-252, in that order; a NaN fails both comparisons and is caught last
-            if (p < dmin) p = dmin;
-            if (p > dmax) p = dmax;
-            if (p != p) p = dmin;
-            if (g > dmin && g < dmax) {             // :253
-                const float thr = fmaxf(__fdiv_rn(g, p), __fdiv_rn(p, g));
-                const float diff = g - p, sq = diff * diff;
-                const float err = log_rn(p) - log_rn(g);
-                s[0] += 1.0;
-                s[1] += thr < 1.25f ? 1.0 : 0.0;
-                s[2] += thr < 1.5625f ? 1.0 : 0.0;
-                s[3] += thr < 1.953125f ? 1.0 : 0.0;
-                s[4] += (double)sq;
-                s[5] += (double)__fdiv_rn(fabsf(diff), g);
-                s[6] += (double)__fdiv_rn(sq, g);
-                s[7] += (double)err;
-                s[8] += (double)(err * err);
-                s[9] += (double)fabsf(log10_rn(p) - log10_rn(g));
+            const float p = eval_clamp(to_f32(pred[b * HW + i]), dmin, dmax);
+            if (eval_valid(g, dmin, dmax)) {
+                float t[NSUM];                      // the per-pixel terms: evalterms.h
+                eval_terms(g, p, t);
+#pragma unroll
+                for (int k = 0; k < NSUM; ++k) s[k] += (double)t[k];
             }
         }
         if (seg) {

@@ -187,6 +187,29 @@ class FrameStore:
         self._turn = 1 - self._turn
         return _frames_of(buf, offs, sizes)
 
+    def record_gt(self, indices):
+        """[(depth_mm uint16 (h,w), labels uint8 (h,w))] of up to 16 samples as VIEWS of the device arena: the ground truth exactly as
+        the records hold it, for evaluate.FrameMetrics.update - no widen launch, no copy.  where='device' only."""
+        if self.where != "device":
+            raise ValueError("record_gt needs the records in HBM (where='device'); a pinned store goes through frames()")
+        out = []
+        for i in _check_batch(indices, len(self)):
+            h, w = self.sizes[i]
+            _, o_d, o_l, _ = plane_layout(h, w)
+            o = self.offsets[i]
+            out.append((self.arena[o + o_d:o + o_d + 2 * h * w].view(torch.uint16).view(h, w), self.arena[o + o_l:o + o_l + h * w].view(h, w)))
+        return out
+
+    def record_rgb(self, indices):
+        """[rgb uint8 (h,w,3)] of up to 16 samples as views of the device arena (record_gt's companion: frames() without the depth)."""
+        if self.where != "device":
+            raise ValueError("record_rgb needs the records in HBM (where='device'); a pinned store goes through frames()")
+        out = []
+        for i in _check_batch(indices, len(self)):
+            h, w = self.sizes[i]
+            out.append(self.arena[self.offsets[i]:self.offsets[i] + 3 * h * w].view(h, w, 3))
+        return out
+
 
 class StreamSource:
     """frames(indices) without a store, for datasets that do not fit: every call decodes its samples through the pool, gathers the

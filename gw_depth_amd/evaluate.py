@@ -11,6 +11,11 @@ NestedTensor masks.  The visualisation switches (save_dense / save_line) are out
 `LineMetrics` scores the line detector the way the reference does offline (structural AP and F-score at 5 / 10 / 15 after L-CNN's
 line NMS; evaluation/eval_post_online.py, eval-sAP-glassrgbd.py, eval-fscore-glassrgbd.py), accumulated on the device by
 gwd_line_score, one launch per batch; `evaluate` feeds it when args.line_ap is set together with --with_line.
+
+`FrameMetrics` scores what InferenceSession.predict_frames returns - depth and labels at every frame's own size, with or without
+the mirror ensemble - against the ground truth as the loaders keep it (millimetres and raw label bytes), by region (all / glass /
+non-glass / GT-depth bins), one gwd_eval_frames launch per call, per-image records kept and mergeable across ranks;
+`evaluate_frames` walks a dataset.FrameStore or StreamSource through both.
 """
 import numpy as np
 import torch
@@ -174,6 +179,222 @@ class LineMetrics:
                 tag = "%g_nms%s" % (st, ("%.3f" % thr).replace(".", "_"))
                 out["sAP" + tag], out["sF" + tag] = ap, f
         return out
+
+
+def _measures_from_sums(s):
+    """(..., 10) raw sums -> (..., 9) measures (METRIC_NAMES order), NaN where the count is zero: the closing step of the kernel."""
+    with np.errstate(all="ignore"):
+        n = s[..., 0]
+        me, me2 = s[..., 7] / n, s[..., 8] / n
+        return np.stack([np.sqrt(me2 - me * me) * 100.0, s[..., 5] / n, s[..., 9] / n, np.sqrt(s[..., 4] / n), s[..., 6] / n,
+                         np.sqrt(me2), s[..., 1] / n, s[..., 2] / n, s[..., 3] / n], axis=-1)
+
+
+class FrameMetrics:
+    """Depth / segmentation metrics of predict_frames results at frame size, by region, kept per image (gwd_eval_frames).
+
+    Regions: "all", "glass" (GT label > 0), "nonglass", and "bin0".. for depth_bins = ascending edges in metres (bin k holds
+    edges[k] <= GT depth < edges[k+1]; at most 8 bins).  Every image fills one record (raw sums, measures, confusion) in HBM;
+    `running` (R,10) and `confusion` (4,) are the device-side totals in the order the images were fed - an image whose region has
+    no valid pixel is left out of that region's mean, and running[:, 9] counts the images that entered.  compute() reads the records
+    back once and folds them in ascending id order, so its result does not depend on how the images were split over calls or ranks."""
+
+    def __init__(self, device, min_depth_eval=1e-3, max_depth_eval=10.0, depth_bins=None, capacity_images=4096):
+        self.device = torch.device(device)
+        self.min_d, self.max_d = float(min_depth_eval), float(max_depth_eval)
+        self.edges = tuple(float(e) for e in (depth_bins if depth_bins is not None else ()))
+        if len(self.edges) == 1 or len(self.edges) > hip.EVAL_FRAMES_MAX_BINS + 1:
+            raise ValueError("depth_bins: 2..%d ascending edges (or none), got %d" % (hip.EVAL_FRAMES_MAX_BINS + 1, len(self.edges)))
+        if any(not b >= a for a, b in zip(self.edges, self.edges[1:])):
+            raise ValueError("depth_bins must ascend, got %r" % (self.edges,))
+        self.n_bins = max(len(self.edges) - 1, 0)
+        self.regions = ["all", "glass", "nonglass"] + ["bin%d" % k for k in range(self.n_bins)]
+        self.capacity = int(capacity_images)
+        if self.capacity < 1:
+            raise ValueError("capacity_images must be positive")
+        R, dev = len(self.regions), self.device
+        self.sums = torch.empty(self.capacity, R, 10, dtype=torch.float64, device=dev)
+        self.measures = torch.empty(self.capacity, R, 9, dtype=torch.float64, device=dev)
+        self.conf = torch.empty(self.capacity, 4, dtype=torch.int64, device=dev)
+        self.running = torch.zeros(R, 10, dtype=torch.float64, device=dev)
+        self.confusion = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._ws = torch.zeros(hip.EVAL_FRAMES_WS_BYTES, dtype=torch.uint8, device=dev)      # the tickets start as zeros, once
+        self.images_seen = 0
+        self._ids = []
+        self._host = None              # a merged object: (ids, sums, measures, conf) host arrays instead of device records
+
+    def reset(self):
+        self.running.zero_()
+        self.confusion.zero_()
+        self.images_seen, self._ids, self._host = 0, [], None
+
+    def update(self, result, gt, ids=None):
+        """result: the dict of predict_frames ("depth" (B,Fh,Fw) fp32, "labels" (B,Fh,Fw) uint8); gt: [(depth_mm (fh,fw), labels
+        (fh,fw) uint8)] per frame, on the device - int32 millimetres as FrameStore.frames() gives them, or the 16-bit plane of a
+        record (uint16 / int16 view, FrameStore.record_gt); ids: one integer per frame (default: the running image count).  The
+        (fh, fw) of every pair are checked on the host against the planes of the result (each fits, the largest fills them).  One
+        launch, nothing to wait for."""
+        if self._host is not None:
+            raise RuntimeError("a merged FrameMetrics takes no updates")
+        depth, labels = result["depth"], result["labels"]
+        if depth.dim() != 3 or depth.dtype != torch.float32 or labels.dtype != torch.uint8 or labels.shape != depth.shape:
+            raise ValueError("FrameMetrics.update: depth (B,Fh,Fw) fp32 and labels (B,Fh,Fw) uint8 expected, got %s %s / %s %s"
+                             % (tuple(depth.shape), depth.dtype, tuple(labels.shape), labels.dtype))
+        B, Fh, Fw = depth.shape
+        if not 0 < B <= hip.EVAL_FRAMES_BATCH or len(gt) != B:
+            raise ValueError("FrameMetrics.update: 1..%d frames per call with one ground-truth pair each, got %d and %d"
+                             % (hip.EVAL_FRAMES_BATCH, B, len(gt)))
+        pairs = []
+        for i, (dmm, lab) in enumerate(gt):
+            if dmm.dtype not in (torch.int32, torch.uint16, torch.int16) or lab.dtype != torch.uint8:
+                raise TypeError("FrameMetrics.update: frame %d: depth_mm int32 / uint16 / int16 and labels uint8 expected, got %s, %s"
+                                % (i, dmm.dtype, lab.dtype))
+            if dmm.dim() != 2 or lab.shape != dmm.shape or dmm.shape[0] < 1 or dmm.shape[1] < 1 or dmm.shape[0] > Fh or dmm.shape[1] > Fw:
+                raise ValueError("FrameMetrics.update: frame %d: ground truth %s / %s does not fit the %d x %d result"
+                                 % (i, tuple(dmm.shape), tuple(lab.shape), Fh, Fw))
+            if dmm.element_size() != gt[0][0].element_size():
+                raise TypeError("FrameMetrics.update: the depth planes of one call have one width")
+            pairs.append((dmm.contiguous(), lab.contiguous()))
+        if (max(d.shape[0] for d, _ in pairs), max(d.shape[1] for d, _ in pairs)) != (Fh, Fw):
+            raise ValueError("FrameMetrics.update: predict_frames sizes its planes by the largest frame of the call, %d x %d; the "
+                             "ground truth's largest is %d x %d - these are not the same frames"
+                             % (Fh, Fw, max(d.shape[0] for d, _ in pairs), max(d.shape[1] for d, _ in pairs)))
+        ids = list(range(self.images_seen, self.images_seen + B)) if ids is None else [int(i) for i in ids]
+        if len(ids) != B:
+            raise ValueError("FrameMetrics.update: %d ids for %d frames" % (len(ids), B))
+        if self.images_seen + B > self.capacity:
+            raise RuntimeError("FrameMetrics: %d images exceed capacity_images = %d" % (self.images_seen + B, self.capacity))
+        rc = _lib().eval_frames(depth.contiguous(), labels.contiguous(), pairs, self.min_d, self.max_d, self.edges, self._ws,
+                                self.images_seen, self.sums, self.measures, self.conf, self.running, self.confusion)
+        if rc != 0:
+            raise RuntimeError("gwd_eval_frames failed with status %d" % rc)
+        self.images_seen += B
+        self._ids += ids
+
+    # ---------------------------------------------------------------------------------------------- host side
+    def _records(self):
+        """(ids, sums, measures, conf) host arrays in feeding order: ONE device->host copy."""
+        if self._host is not None:
+            return self._host
+        n, R = self.images_seen, len(self.regions)
+        ids = np.asarray(self._ids, dtype=np.int64)
+        if n == 0:
+            return ids, np.zeros((0, R, 10)), np.zeros((0, R, 9)), np.zeros((0, 4), dtype=np.int64)
+        flat = torch.cat([self.sums[:n].reshape(-1), self.measures[:n].reshape(-1), self.conf[:n].view(torch.float64).reshape(-1)])
+        host = flat.cpu().numpy()
+        a, b = n * R * 10, n * R * 19
+        return ids, host[:a].reshape(n, R, 10), host[a:b].reshape(n, R, 9), host[b:].view(np.int64).reshape(n, 4)
+
+    def per_image(self):
+        """Host arrays {"ids" (n,), "sums" (n,R,10), "measures" (n,R,9), "confusion" (n,4)} in feeding order."""
+        ids, sums, measures, conf = self._records()
+        return {"ids": ids.copy(), "sums": sums.copy(), "measures": measures.copy(), "confusion": conf.copy()}
+
+    def state(self):
+        """A picklable host snapshot of the per-image records (numpy arrays and plain values) for FrameMetrics.merge."""
+        out = self.per_image()
+        out.update(min_depth_eval=self.min_d, max_depth_eval=self.max_d, depth_bins=self.edges)
+        return out
+
+    @classmethod
+    def merge(cls, states):
+        """One metrics object over the records of several state()s (ranks, or calls): compute() folds them in ascending id order.
+        The states must share depth range and bins; an id that occurs twice raises."""
+        states = list(states)
+        if not states:
+            raise ValueError("FrameMetrics.merge: no states")
+        key = lambda s: (float(s["min_depth_eval"]), float(s["max_depth_eval"]), tuple(float(e) for e in s["depth_bins"]))
+        if any(key(s) != key(states[0]) for s in states[1:]):
+            raise ValueError("FrameMetrics.merge: the states were taken with different depth ranges or bins")
+        ids = np.concatenate([np.asarray(s["ids"], dtype=np.int64) for s in states])
+        if len(set(ids.tolist())) != ids.size:
+            seen, dup = set(), set()
+            for i in ids.tolist():
+                (dup if i in seen else seen).add(i)
+            raise ValueError("FrameMetrics.merge: image ids occur twice: %s" % sorted(dup)[:8])
+        m = cls.__new__(cls)
+        m.device = torch.device("cpu")
+        m.min_d, m.max_d, m.edges = key(states[0])
+        m.n_bins = max(len(m.edges) - 1, 0)
+        m.regions = ["all", "glass", "nonglass"] + ["bin%d" % k for k in range(m.n_bins)]
+        m._host = (ids, np.concatenate([s["sums"] for s in states]), np.concatenate([s["measures"] for s in states]),
+                   np.concatenate([s["confusion"] for s in states]))
+        m.images_seen, m._ids, m.capacity = int(ids.size), ids.tolist(), int(ids.size)
+        return m
+
+    def compute(self):
+        """One device->host copy of the records; they are folded in ascending id order with the kernel's rule (an image enters a
+        region's mean when it has a valid pixel there).  Region "all" under the reference's keys (METRIC_NAMES and the five
+        segmentation scores, closed as DenseMetrics.compute does), the others as "glass/rms", "bin0/rms", ...; "pixel/<key>" are the
+        pixel-weighted variants (the measures of the summed raw sums); "n_images": images per region."""
+        ids, sums, measures, conf = self._records()
+        order = np.argsort(ids, kind="stable")
+        R = len(self.regions)
+        run, total = np.zeros((R, 10)), np.zeros((R, 10))
+        for i in order:                                        # sequential f64 adds: the kernel's own order when ids ascend
+            for r in range(R):
+                if sums[i, r, 0] != 0:
+                    run[r, :9] += measures[i, r]
+                    run[r, 9] += 1
+            total += sums[i]
+        out = {}
+        c = torch.from_numpy(conf.sum(0)).to(torch.float64).reshape(2, 2)
+        if float(c.sum()) > 0:
+            pos, res, tp = c.sum(1), c.sum(0), c.diagonal()
+            iou = tp / torch.clamp(pos + res - tp, min=1.0) * 100
+            for lab, v in zip(SEG_LABELS, iou):
+                out[lab] = float(v)
+            out["Pixel accuracy"] = float(tp.sum() / pos.sum() * 100)
+            out["Mean accuracy"] = float((tp / torch.clamp(pos, min=1.0)).mean() * 100)
+            out["Mean IU"] = float(iou.mean())
+        pix = _measures_from_sums(total)
+        for r, name in enumerate(self.regions):
+            pre = "" if r == 0 else name + "/"
+            for k, m in enumerate(METRIC_NAMES):
+                if run[r, 9] > 0:
+                    out[pre + m] = float(run[r, k] / run[r, 9])
+                if total[r, 0] > 0:
+                    out["pixel/" + pre + m] = float(pix[r, k])
+        out["n_images"] = {name: int(run[r, 9]) for r, name in enumerate(self.regions)}
+        return out
+
+    def worst(self, k, key="rms", region="all"):
+        """The k images with the largest `key` in `region` as (id, value) pairs, largest first (ties: lower id first); images
+        without a value there (NaN) are left out."""
+        ids, _, measures, _ = self._records()
+        v = measures[:, self.regions.index(region), METRIC_NAMES.index(key)]
+        keep = np.nonzero(~np.isnan(v))[0]
+        keep = keep[np.lexsort((ids[keep], -v[keep]))]
+        return [(int(ids[i]), float(v[i])) for i in keep[:max(int(k), 0)]]
+
+
+@torch.no_grad()
+def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size=1024, max_size=1024, pad_to=None, depth_bins=None,
+                    metrics=None):
+    """Scores the samples `indices` (default: all) of a dataset.FrameStore / StreamSource through session.predict_frames at the
+    frames' own resolution: `batch` frames per call (at most 16, 8 with ensemble=True), one gwd_eval_frames launch behind each,
+    no host sync before the closing copy.  A device-resident FrameStore hands its 16-bit depth planes over in place (record_gt).
+    -> metrics.compute() plus "names": {sample index: name} for FrameMetrics.worst.  Pass `metrics` to keep the accumulator."""
+    indices = list(range(len(source))) if indices is None else [int(i) for i in indices]
+    limit = hip.EVAL_FRAMES_BATCH // 2 if ensemble else hip.EVAL_FRAMES_BATCH
+    if not 0 < int(batch) <= limit:
+        raise ValueError("evaluate_frames: 1..%d frames per call%s, got %r" % (limit, " with ensemble=True" if ensemble else "", batch))
+    if metrics is None:
+        metrics = FrameMetrics(session._device(), session.min_depth, session.max_depth, depth_bins=depth_bins,
+                               capacity_images=max(len(indices), 1))
+    in_place = getattr(source, "where", None) == "device" and hasattr(source, "record_gt")
+    for at in range(0, len(indices), int(batch)):
+        idx = indices[at:at + int(batch)]
+        if in_place:                                           # views of the records: no widen launch, no copy
+            rgb, gt = source.record_rgb(idx), source.record_gt(idx)
+        else:
+            frames = source.frames(idx)
+            rgb, gt = [f[0] for f in frames], [(f[1], f[2]) for f in frames]
+        res = session.predict_frames(rgb, size=size, max_size=max_size, ensemble=ensemble, pad_to=pad_to)
+        metrics.update(res, gt, ids=idx)
+    out = metrics.compute()
+    out["names"] = {i: source.name(i) for i in indices}
+    return out
 
 
 def close_line_scores(sorted_flags, n_gt):

@@ -40,6 +40,7 @@ ENTRY_POINTS = [
     "gwd_pyr_tail_forward", "gwd_pyr_tail_backward", "gwd_pyr_tail_fold_wgrad",
     "gwd_widen_u16_batch",
     "gwd_line_nms",
+    "gwd_eval_frames",
 ]
 
 
@@ -110,6 +111,14 @@ class WidenJob(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n", ctypes.c_int64)]
 
 
+class FrameEvalJob(ctypes.Structure):
+    """gwd_frame_eval_job (include/gwdepth.h)."""
+    _fields_ = [("gt_depth_mm", ctypes.c_void_p), ("gt_label", ctypes.c_void_p), ("fh", ctypes.c_int32), ("fw", ctypes.c_int32)]
+
+
+EVAL_FRAMES_BATCH = 16    # gwd_eval_frames: frames per call
+EVAL_FRAMES_MAX_BINS = 8
+EVAL_FRAMES_WS_BYTES = 128 + 16 * 256 * 32 + 16 * 5 * 256 * 160      # GWD_EVAL_FRAMES_WS_BYTES; the first 128 bytes start as zeros
 WIDEN_BATCH = 16          # gwd_widen_u16_batch jobs: the depth planes of one batch
 AUGMENT_BATCH = 16        # frames per grouped augmentation launch
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
@@ -289,6 +298,8 @@ class HipLibrary:
         L.gwd_pyr_tail_fold_wgrad.argtypes = [vp, pvp, i32, vp, i32, i32, i32, vp]
         L.gwd_widen_u16_batch.argtypes = [ctypes.POINTER(WidenJob), i32, vp]
         L.gwd_line_nms.argtypes = [vp] * 4 + [ctypes.c_double, f32] + [vp] * 4 + [i32] * 4 + [vp]
+        L.gwd_eval_frames.argtypes = [ctypes.POINTER(FrameEvalJob), i32, vp, vp, i32, i32, i32, f32, f32, ctypes.POINTER(f32), i32,
+                                      vp, i64, vp, vp, vp, vp, vp, vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -633,6 +644,39 @@ class HipLibrary:
             r.n = dst.numel()
             ts += [src, dst]
         self._check(self.lib.gwd_widen_u16_batch(recs, len(jobs), self._stream(*ts)), "gwd_widen_u16_batch")
+
+    def eval_frames(self, depth, label, gt, dmin, dmax, bin_edges, workspace, offset, sums, measures, conf, running, confusion):
+        """gwd_eval_frames.  depth (B,Fh,Fw) fp32 and label (B,Fh,Fw) uint8 as predict_frames returns them; gt: B pairs (depth_mm,
+        labels) of contiguous (fh,fw) tensors, depth_mm 2 or 4 bytes wide (all alike), labels uint8; bin_edges: host floats (R - 2
+        of them, or none); workspace EVAL_FRAMES_WS_BYTES uint8 whose first 128 bytes started as zeros; sums (N,R,10) / measures
+        (N,R,9) f64 and conf (N,4) int64 take the records offset .. offset + B - 1; running (R,10) f64 and confusion (4,) int64
+        accumulate.  Returns the library's status for bad arguments (nothing launched) instead of raising: 0 on success."""
+        B, Fh, Fw = depth.shape
+        R = running.shape[0]
+        n_bins = max(len(bin_edges) - 1, 0)
+        if depth.dtype != torch.float32 or label.dtype != torch.uint8 or tuple(label.shape) != (B, Fh, Fw) or len(gt) != B:
+            raise ValueError("eval_frames: depth (B,Fh,Fw) fp32, label (B,Fh,Fw) uint8 and B ground-truth pairs expected")
+        if R != 3 + n_bins or tuple(running.shape) != (R, 10) or sums.shape[1:] != (R, 10) or measures.shape[1:] != (R, 9) \
+                or conf.shape[1:] != (4,) or confusion.numel() != 4 or workspace.numel() < EVAL_FRAMES_WS_BYTES:
+            raise ValueError("eval_frames: output shapes do not fit %d regions" % (3 + n_bins))
+        if not 0 <= offset <= min(sums.shape[0], measures.shape[0], conf.shape[0]) - B:
+            raise ValueError("eval_frames: records %d .. %d lie outside the output buffers" % (offset, offset + B - 1))
+        for t, dt in ((sums, torch.float64), (measures, torch.float64), (running, torch.float64), (conf, torch.int64), (confusion, torch.int64)):
+            if t.dtype != dt:
+                raise TypeError("eval_frames: expected %s, got %s" % (dt, t.dtype))
+        recs = (FrameEvalJob * max(B, 1))()
+        ts = [depth, label, workspace, sums, measures, conf, running, confusion]
+        width = gt[0][0].element_size() if B else 4
+        for r, (dmm, lab) in zip(recs, gt):
+            if dmm.dim() != 2 or lab.shape != dmm.shape or lab.dtype != torch.uint8 or dmm.element_size() != width \
+                    or dmm.is_floating_point():
+                raise ValueError("eval_frames: ground truth is (depth_mm (fh,fw) of one integer width, labels (fh,fw) uint8) per frame")
+            r.gt_depth_mm, r.gt_label, r.fh, r.fw = _ptr(dmm), _ptr(lab), dmm.shape[0], dmm.shape[1]
+            ts += [dmm, lab]
+        edges = (ctypes.c_float * (n_bins + 1))(*[float(e) for e in bin_edges]) if n_bins else None
+        return self.lib.gwd_eval_frames(recs, B, _ptr(depth), _ptr(label), Fh, Fw, width, float(dmin), float(dmax), edges, n_bins,
+                                        _ptr(workspace), int(offset), _ptr(sums), _ptr(measures), _ptr(conf), _ptr(running),
+                                        _ptr(confusion), self._stream(*ts))
 
     @staticmethod
     def _tok(t):

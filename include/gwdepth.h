@@ -798,6 +798,46 @@ typedef struct {
 } gwd_widen_job;
 int gwd_widen_u16_batch(const gwd_widen_job *jobs, int32_t n_jobs, void *stream);
 
+/* Dense metrics of up to GWD_EVAL_FRAMES_BATCH frames at FRAME size, by region, in ONE launch (csrc/evalframes.hip): what
+ * InferenceSession.predict_frames returns, scored against the ground truth as the data set stores it.  The arithmetic is
+ * gwd_eval_accumulate's (src/engine_glassrgbd.py:249-253, src/util/metrics.py:198-218 and :37-56), pixel for pixel.
+ *   depth [n_jobs][Fh][Fw] fp32, label [n_jobs][Fh][Fw] uint8: frame i sits top-left in plane i; whatever lies outside its
+ *   (fh, fw) is never read as a pixel.  `jobs` is a HOST array, the records travel in the kernel arguments: gt_depth_mm = the
+ *   frame's fh x fw millimetres, densely packed, gt_bytes (2: unsigned 16-bit, the plane of a sample's record; 4: int32) wide;
+ *   gt_label = its fh x fw raw label bytes.  bin_edges: HOST array of n_bins + 1 ascending fp32 values, n_bins 0..8.
+ * Per pixel: g = float(mm) / 1000 (IEEE), glass = raw label > 0 (src/datasets/glassrgbd_norhint.py:273,275); the prediction is
+ * clamped (< min -> min, > max -> max, NaN -> min, in that order); the pixel is valid when min < g < max and then adds the ten
+ * terms of GWD_EVAL_NSUM to region 0 (all), to region 1 (glass) or 2 (non-glass), and to region 3 + k when
+ * bin_edges[k] <= g < bin_edges[k + 1] (at most one).  R = 3 + n_bins.  The confusion counts take every pixel of the frame whose
+ * predicted label is 0 or 1: [glass * 2 + label].
+ * Outputs, image record i of the call at index image_offset + i, every element of the n_jobs records written:
+ *   sums [..][R][10] f64 the raw sums; measures [..][R][9] f64 in the order of gwd_eval_accumulate, NaN where the region of the
+ *   image has no valid pixel; conf [..][4] int64.
+ *   running [R][10] f64 IN/OUT: += the nine measures of every image whose region is not empty, in image order, and [9] += 1 for
+ *   each of them (the reference's running sum would turn NaN on an empty image; here the count says how many entered);
+ *   confusion [4] int64 IN/OUT.
+ *   workspace: GWD_EVAL_FRAMES_WS_BYTES, 16-byte aligned; its first 128 bytes (the tickets) must be ZERO before the first call on
+ *   it and are zero again after every call; calls that share a workspace must be ordered on one stream.
+ * No allocation, no memset, no host synchronisation, no floating-point atomics (one integer ticket per workgroup).  A frame is
+ * partitioned by fh * fw alone and folded in a fixed order: bit-reproducible, and a frame's record does not depend on its slot,
+ * on the other frames, on Fh x Fw or on alignment.  16-byte / 8-byte accesses when Fw % 8 == 0, fw % 8 == 0, depth and
+ * gt_depth_mm are 16-byte and label and gt_label 8-byte aligned; element-wise otherwise.  All shapes are accepted.
+ * -1 on bad arguments (a null pointer, n_jobs outside 1..16, a frame larger than Fh x Fw or empty, n_bins outside 0..8, edges
+ * that descend or are NaN, min_depth >= max_depth, a negative offset), -2 when gt_bytes is not 2 or 4, -3 when a gt_depth_mm is
+ * not aligned to its element; nothing is launched then.                                                                        */
+#define GWD_EVAL_FRAMES_BATCH 16
+#define GWD_EVAL_FRAMES_MAX_BINS 8
+#define GWD_EVAL_FRAMES_WS_BYTES (128 + 16 * 256 * 32 + 16 * 5 * 256 * 160)
+typedef struct {
+    const void *gt_depth_mm;
+    const uint8_t *gt_label;
+    int32_t fh, fw;
+} gwd_frame_eval_job;
+int gwd_eval_frames(const gwd_frame_eval_job *jobs, int32_t n_jobs, const float *depth, const uint8_t *label, int32_t Fh,
+                    int32_t Fw, int32_t gt_bytes, float min_depth, float max_depth, const float *bin_edges, int32_t n_bins,
+                    void *workspace, int64_t image_offset, double *sums, double *measures, int64_t *conf, double *running,
+                    int64_t *confusion, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
