@@ -92,7 +92,8 @@ class FlatAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         self.ts.optimizer_step()
-        self._step_t.fill_(float(self.ts.step_count))
+        if self.ts.guard == "off":                   # guarded: Adam's step is a device counter, read when a state dict is asked for
+            self._step_t.fill_(float(self.ts.step_count))
 
     def zero_grad(self, set_to_none=False):
         self.ts.zero_grad()
@@ -105,7 +106,7 @@ class FlatAdamW(torch.optim.Optimizer):
                 i += 1
 
     def state_dict(self):
-        self._step_t.fill_(float(self.ts.step_count))
+        self._step_t.fill_(float(self.ts.applied_steps()))        # guard="skip": the applied steps, read once
         sd = super().state_dict()
         state = {k: dict(v) for k, v in sd["state"].items()}
         for i, p in self._indexed():
@@ -144,6 +145,9 @@ class FlatAdamW(torch.optim.Optimizer):
         if len(steps) > 1:
             raise ValueError("per-parameter step counts differ (%s): not a state this fused AdamW can continue" % sorted(steps))
         ts.step_count = steps.pop() if steps else 0
+        if ts.guard == "skip":
+            ts._health.seed_applied(ts.step_count)
+            ts._pending_health, ts._health_seen = [], None
         self._step_t.fill_(float(ts.step_count))
         self._link()
 

@@ -28,6 +28,7 @@ import torch
 import torch.distributed as dist
 
 from . import hip, ops
+from .health import HealthState
 from .criteria import PackedTargets, target_capacity
 from .model import NestedTensor
 
@@ -108,7 +109,13 @@ def _align(n):
 
 class TrainStep:
     def __init__(self, model, criterions, cfg, compute_dtype=torch.float32, bucket_mb=32.0, process_group=None,
-                 check_finite=True, data_parallel=True, graph=False, segments=None, max_graphs=None, capture_after=1):
+                 check_finite=True, data_parallel=True, graph=False, segments=None, max_graphs=None, capture_after=1,
+                 guard="off", stats_every=0, ring=64, max_consecutive_skips=8):
+        if guard not in ("off", "skip"):
+            raise ValueError("guard must be 'off' or 'skip', got %r" % (guard,))
+        if int(stats_every) < 0 or int(max_consecutive_skips) < 0:
+            raise ValueError("stats_every and max_consecutive_skips must be >= 0")
+        self.guard, self.stats_every, self.max_consecutive_skips = guard, int(stats_every), int(max_consecutive_skips)
         self.model, self.cfg = model, cfg
         self.criterion, self.criterion_depth, self.criterion_seg, self.criterion_plane = criterions
         self.compute_dtype = compute_dtype
@@ -122,6 +129,8 @@ class TrainStep:
         self._pool = None
         self._gstream = None
         self._pending_checks = []
+        self._pending_health = []         # guard="skip": control blocks on their way to the host, examined one step late
+        self._health_seen = None          # the newest one examined
         self.weights = None           # built after the parameters moved into the flat buffer
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (data_parallel and dist.is_available() and dist.is_initialized()) else 1
@@ -156,6 +165,10 @@ class TrainStep:
         self.flat_v = torch.zeros_like(self.flat_p)
         self.flat_p16 = torch.zeros(off, dtype=torch.bfloat16, device=dev) if compute_dtype == torch.bfloat16 else None
         self.sq = torch.zeros(1, dtype=torch.float64, device=dev)
+        # segment tables, statistics, control block and ring of the guarded step; None on the default path
+        self._health = None
+        if guard != "off" or self.stats_every > 0:
+            self._health = HealthState(self.names, offs, {n: named[n].numel() for n in self.names}, off, dev, ring, hip.library())
         self.params = {}
         for n in self.names:
             p, o, k = named[n], offs[n], named[n].numel()
@@ -376,25 +389,100 @@ class TrainStep:
     def zero_grad(self):
         self.flat_g.zero_()
 
-    def optimizer_step(self):
+    def optimizer_step(self, loss=None):
+        """Clip + AdamW on the flat buffers.  guard="skip": per-tensor statistics of flat_g, the decision on the device, then AdamW
+        that stores nothing when a gradient element is not finite; `loss` (a device scalar, optional) is recorded, it never decides."""
         cfg, lib = self.cfg, hip.library()
         self.step_count += 1
-        t = self.step_count
-        bc1, bc2 = 1 - 0.9 ** t, 1 - 0.999 ** t
-        self.sq.zero_()
-        lib.sqnorm(self.flat_g, self.sq, self.total)
         gs = 1.0 / self.world
         opt = getattr(self, "optimizer", None)      # checkpoint.FlatAdamW: a StepLR may have moved the groups' rates
         lr0, lr1 = opt.lrs() if opt is not None else (cfg.lr, cfg.lr_backbone)
-        for lo, hi, lr in ((0, self.split, lr0), (self.split, self.total, lr1)):
-            if hi > lo:
+        groups = [(lo, hi, lr) for lo, hi, lr in ((0, self.split, lr0), (self.split, self.total, lr1)) if hi > lo]
+        hs = self._health
+        take = self.stats_every > 0 and self.step_count % self.stats_every == 0
+        if self.guard == "skip":
+            # Adam's step is the device counter `applied`: a skipped step leaves it (and so the bias corrections) alone
+            hs.grad_stats(lib, self.flat_g)
+            hs.decide(lib, None if loss is None else loss.detach().reshape(1).float(), 0.9, 0.999, cfg.clip_max_norm, gs)
+            for lo, hi, lr in groups:
+                lib.adamw_step_guarded(self.flat_p[lo:hi], self.flat_g[lo:hi], self.flat_m[lo:hi], self.flat_v[lo:hi],
+                                       None if self.flat_p16 is None else self.flat_p16[lo:hi], hs.ctl, hi - lo, lr, 0.9, 0.999,
+                                       1e-8, cfg.weight_decay, cfg.clip_max_norm, gs)
+            if self.check_finite:
+                self._pending_health.append((self.step_count,) + hs.snapshot())
+        else:
+            t = self.step_count
+            bc1, bc2 = 1 - 0.9 ** t, 1 - 0.999 ** t
+            self.sq.zero_()
+            lib.sqnorm(self.flat_g, self.sq, self.total)
+            for lo, hi, lr in groups:
                 lib.adamw_step(self.flat_p[lo:hi], self.flat_g[lo:hi], self.flat_m[lo:hi], self.flat_v[lo:hi],
                                None if self.flat_p16 is None else self.flat_p16[lo:hi], self.sq, hi - lo, lr, 0.9, 0.999,
                                1e-8, cfg.weight_decay, bc1, bc2, cfg.clip_max_norm, gs)
+            if take:
+                hs.grad_stats(lib, self.flat_g)
+        if take:
+            hs.param_stats(lib, self.flat_p)
 
     def grad_norm(self):
-        """Un-clipped global gradient norm of the last step (host sync)."""
+        """Un-clipped global gradient norm of the last step (host sync); with the guard on, the ordered fold's value (over the finite
+        elements)."""
+        if self.guard == "skip":
+            return math.sqrt(self._health.read_ctl()["sq"]) / self.world
         return math.sqrt(float(self.sq.item())) / self.world
+
+    # ------------------------------------------------------------------ read-backs of the guarded step: one D2H copy each
+    def _need_health(self, what, guard=True):
+        if self._health is None or (guard and self.guard != "skip"):
+            raise RuntimeError("%s needs TrainStep(%s)" % (what, 'guard="skip"' if guard else 'guard="skip") or TrainStep(stats_every=k'))
+        return self._health
+
+    def health(self, wait=True):
+        """{"applied", "skipped", "streak", "sq", "bc1", "bc2", "loss_finite", "last": the newest ring record}.  wait=True reads the
+        control block now (one blocking 64-byte copy); wait=False returns what the lagged poll of check_finite saw last (None before
+        its first look) and never touches the device."""
+        hs = self._need_health("health()")
+        if not wait:
+            return self._health_seen
+        h = hs.read_ctl()
+        h["last"]["grad_norm"] = math.sqrt(h["sq"]) / self.world
+        return h
+
+    def history(self):
+        """The ring in step order: [{"step", "apply", "grad_norm", "clip_coef", "loss", "nonfinite_total"}], at most `ring` entries."""
+        return self._need_health("history()").read_ring()
+
+    def tensor_stats(self):
+        """{name: (grad_norm, grad_absmax, grad_nonfinite, param_norm)} of the last pass over flat_g (every step with the guard on,
+        every stats_every-th without) and over flat_p (every stats_every-th step; None before).  Norms are over the finite elements."""
+        hs = self._need_health("tensor_stats()", guard=False)
+        g, p = hs.read_stats()
+        w = float(self.world)
+        out = {}
+        for i, n in enumerate(self.names):
+            grad = (math.sqrt(float(g[i]["sumsq"])) / w, float(g[i]["absmax"]) / w, int(g[i]["nonfinite"])) if hs.have_grad else (None, None, None)
+            out[n] = grad + (math.sqrt(float(p[i]["sumsq"])) if hs.have_param else None,)
+        return out
+
+    def first_nonfinite(self):
+        """Names of the tensors whose gradient held a NaN or Inf in the last skipped step, in flat-buffer order."""
+        return self._need_health("first_nonfinite()").read_bad()
+
+    def applied_steps(self):
+        """Adam's step: the device counter with the guard on (one D2H copy), step_count otherwise."""
+        return self._health.read_ctl()["applied"] if self.guard == "skip" else self.step_count
+
+    def _poll_health(self, keep=0):
+        while len(self._pending_health) > keep:
+            step_no, slot, ev = self._pending_health.pop(0)
+            if ev is not None:
+                ev.synchronize()
+            h = self._health_seen = HealthState.ctl_dict(slot)
+            h["last"]["grad_norm"] = math.sqrt(h["sq"]) / self.world
+            if h["streak"] > self.max_consecutive_skips:
+                self._pending_health = []
+                raise FloatingPointError("%d optimizer steps in a row skipped for non-finite gradients (step %d, %d elements in the last); "
+                                         "tensors: %r" % (h["streak"], step_no, h["last"]["nonfinite_total"], self.first_nonfinite()))
 
     def forward_backward(self, batch, taps=None):
         """Forward, losses, backward and (N > 1) the bucketed gradient all-reduce; leaves SUMMED grads in flat_g."""
@@ -597,7 +685,10 @@ class TrainStep:
             out, total, terms = self._graph_step(batch) if taps is None else self._on_graph_stream(batch, taps)
         else:
             out, total, terms = self.forward_backward(batch, taps)
-        self.optimizer_step()
+        if self.guard == "skip":
+            self.optimizer_step(total)
+        else:
+            self.optimizer_step()
         if self.check_finite:                       # engine_glassrgbd.py:143-153
             if total.is_cuda and self.use_graph:
                 # graph mode keeps the host a step ahead of the device: the loss goes to pinned memory asynchronously and
@@ -610,6 +701,8 @@ class TrainStep:
                 if not math.isfinite(v):
                     bad = {k: float(t) for k, t in terms.items() if not math.isfinite(float(t))}
                     raise FloatingPointError("Loss is %r at step %d, stopping training (non-finite terms: %r)" % (v, self.step_count, bad))
+            if self.guard == "skip":                # the control block follows the same way: examined one step late in graph mode
+                self._poll_health(keep=1 if (total.is_cuda and self.use_graph) else 0)
         return out, total.detach(), terms
 
     def _queue_finite_check(self, total):
@@ -630,3 +723,4 @@ class TrainStep:
     def flush(self):
         """Examine every outstanding loss (graph mode checks one step late); call at the end of an epoch."""
         self._poll_finite_checks(keep=0)
+        self._poll_health(keep=0)

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GWD_LIB") or os.path.join(_HERE, "libgwdepth_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3, 4
-WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE = 0, 1, 2, 3          # gwd_query_workspace ops
+WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH = 0, 1, 2, 3, 4          # gwd_query_workspace ops
 GATHER_CONV, GATHER_TRANSPOSED, GATHER_UPSAMPLED = 0, 1, 2
 RESAMPLE_BILINEAR_AC, RESAMPLE_NEAREST = 0, 1
 
@@ -41,6 +41,7 @@ ENTRY_POINTS = [
     "gwd_widen_u16_batch",
     "gwd_line_nms",
     "gwd_eval_frames",
+    "gwd_segment_stats", "gwd_health_decide", "gwd_adamw_step_guarded",
 ]
 
 
@@ -119,6 +120,8 @@ class FrameEvalJob(ctypes.Structure):
 EVAL_FRAMES_BATCH = 16    # gwd_eval_frames: frames per call
 EVAL_FRAMES_MAX_BINS = 8
 EVAL_FRAMES_WS_BYTES = 128 + 16 * 256 * 32 + 16 * 5 * 256 * 160      # GWD_EVAL_FRAMES_WS_BYTES; the first 128 bytes start as zeros
+HEALTH_CHUNK = 16384      # GWD_HEALTH_CHUNK: elements per piece of gwd_segment_stats
+HEALTH_RECORD_BYTES, HEALTH_CTL_BYTES, HEALTH_RING_BYTES = 16, 64, 32      # gwd_segment_record / gwd_health_chunk, gwd_health_ctl, gwd_health_record
 WIDEN_BATCH = 16          # gwd_widen_u16_batch jobs: the depth planes of one batch
 AUGMENT_BATCH = 16        # frames per grouped augmentation launch
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
@@ -300,6 +303,9 @@ class HipLibrary:
         L.gwd_line_nms.argtypes = [vp] * 4 + [ctypes.c_double, f32] + [vp] * 4 + [i32] * 4 + [vp]
         L.gwd_eval_frames.argtypes = [ctypes.POINTER(FrameEvalJob), i32, vp, vp, i32, i32, i32, f32, f32, ctypes.POINTER(f32), i32,
                                       vp, i64, vp, vp, vp, vp, vp, vp]
+        L.gwd_segment_stats.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp]
+        L.gwd_health_decide.argtypes = [vp, i32, vp, vp, vp, i32, vp, ctypes.c_double, ctypes.c_double, f32, f32, vp]
+        L.gwd_adamw_step_guarded.argtypes = [vp, vp, vp, vp, vp, vp, i64] + [f32] * 7 + [vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1179,6 +1185,48 @@ class HipLibrary:
         self._check(self.lib.gwd_adamw_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(p16), _ptr(sq), n, lr, b1, b2, eps,
                                             wd, bc1, bc2, max_norm, grad_scale, self._stream(p, g, m, v)),
                     "gwd_adamw_step")
+
+    @staticmethod
+    def _check_bytes(t, nbytes, what):
+        if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() < nbytes:
+            raise ValueError("%s: a flat uint8 buffer of at least %d bytes expected" % (what, nbytes))
+
+    def segment_stats(self, x, seg_begin, seg_end, chunks, partial, out):
+        """gwd_segment_stats.  x flat fp32; seg_begin / seg_end (S,) int64; chunks (n_chunks, 2) int64 = gwd_health_chunk records
+        (engine.chunk_table); partial: uint8, workspace_bytes(WS_HEALTH, n_chunks); out: uint8, S * 16 bytes = S gwd_segment_record."""
+        S, n_chunks = seg_begin.numel(), chunks.shape[0]
+        if x.dtype != torch.float32 or x.dim() != 1:
+            raise TypeError("segment_stats: x is a flat float32 buffer")
+        if seg_begin.dtype != torch.int64 or seg_end.dtype != torch.int64 or seg_end.shape != seg_begin.shape or seg_begin.dim() != 1 or S < 1:
+            raise ValueError("segment_stats: seg_begin and seg_end are (S,) int64 tables, S >= 1")
+        if chunks.dtype != torch.int64 or chunks.dim() != 2 or chunks.shape[1] != 2:
+            raise ValueError("segment_stats: chunks is an (n_chunks, 2) int64 table of gwd_health_chunk records")
+        self._check_bytes(partial, max(n_chunks, 1) * HEALTH_RECORD_BYTES, "segment_stats: partial")
+        self._check_bytes(out, S * HEALTH_RECORD_BYTES, "segment_stats: out")
+        self._check(self.lib.gwd_segment_stats(_ptr(x), _ptr(seg_begin), _ptr(seg_end), S, _ptr(chunks), n_chunks, _ptr(partial), _ptr(out),
+                                               self._stream(x, seg_begin, seg_end, chunks, partial, out)), "gwd_segment_stats")
+
+    def health_decide(self, stats, S, loss, ctl, ring, ring_len, bad, beta1, beta2, max_norm, grad_scale):
+        """gwd_health_decide.  stats: uint8, S gwd_segment_record; loss: None or one device fp32; ctl: uint8, 64 bytes; ring: uint8,
+        ring_len * 32 bytes; bad (S,) int32."""
+        self._check_bytes(stats, S * HEALTH_RECORD_BYTES, "health_decide: stats")
+        self._check_bytes(ctl, HEALTH_CTL_BYTES, "health_decide: ctl")
+        self._check_bytes(ring, ring_len * HEALTH_RING_BYTES, "health_decide: ring")
+        if bad.dtype != torch.int32 or bad.numel() < S:
+            raise ValueError("health_decide: bad is an int32 table of S entries")
+        if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1):
+            raise TypeError("health_decide: loss is one float32 value on the device, or None")
+        self._check(self.lib.gwd_health_decide(_ptr(stats), S, _ptr(loss), _ptr(ctl), _ptr(ring), ring_len, _ptr(bad), float(beta1),
+                                               float(beta2), max_norm, grad_scale, self._stream(stats, loss, ctl, ring, bad)),
+                    "gwd_health_decide")
+
+    def adamw_step_guarded(self, p, g, m, v, p16, ctl, n, lr, b1, b2, eps, wd, max_norm, grad_scale):
+        self._check_bytes(ctl, HEALTH_CTL_BYTES, "adamw_step_guarded: ctl")
+        if any(t.dtype != torch.float32 or t.numel() < n for t in (p, g, m, v)) or (p16 is not None and (p16.dtype != torch.bfloat16 or p16.numel() < n)):
+            raise ValueError("adamw_step_guarded: p, g, m, v are float32 (p16 bfloat16) ranges of at least n elements")
+        self._check(self.lib.gwd_adamw_step_guarded(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(p16), _ptr(ctl), n, lr, b1, b2, eps, wd,
+                                                    max_norm, grad_scale, self._stream(p, g, m, v, ctl)),
+                    "gwd_adamw_step_guarded")
 
 
 _LIB = None

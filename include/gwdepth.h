@@ -87,8 +87,9 @@ const char *gwd_arch(void);
  *   GWD_WS_RESAMPLE_BWD    dims = {B, Ho, Ws, C}   -> `tmp`  of gwd_resample_backward_sep
  *   GWD_WS_EVAL            dims = {B, H*W}         -> `workspace` of gwd_eval_accumulate
  *   GWD_WS_PLANE           dims = {P, H*W}         -> `workspace` of gwd_plane_loss_forward
+ *   GWD_WS_HEALTH          dims = {n_chunks}       -> `partial` of gwd_segment_stats
  * Returns -1 for an unknown op or a wrong dimension count.                                                     */
-enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3 };
+enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3, GWD_WS_HEALTH = 4 };
 int64_t gwd_query_workspace(int32_t op, const int64_t *dims, int32_t ndims);
 
 /* Implicit-GEMM convolution on MFMA with fused epilogue y = act(scale*conv(x,w) + shift + residual).
@@ -837,6 +838,62 @@ int gwd_eval_frames(const gwd_frame_eval_job *jobs, int32_t n_jobs, const float 
                     int32_t Fw, int32_t gt_bytes, float min_depth, float max_depth, const float *bin_edges, int32_t n_bins,
                     void *workspace, int64_t image_offset, double *sums, double *measures, int64_t *conf, double *running,
                     int64_t *confusion, void *stream);
+
+/* Guarded optimizer step and per-tensor statistics of a flat fp32 buffer (csrc/health.hip).
+ *
+ * gwd_segment_stats: segment s of `x` is x[seg_begin[s] : seg_end[s]) (DEVICE int64 tables of S entries; begins are multiples of 8
+ * elements, ends are arbitrary, an empty segment is legal; what lies between two segments is never read).  out[s]:
+ *   sumsq     f64  sum of the squares of the FINITE elements, each square taken in fp64 (exact for an fp32 operand, never inf),
+ *   absmax    f32  largest finite magnitude (0 for none),
+ *   nonfinite i32  number of NaN and +-Inf elements.
+ * `chunks` is a DEVICE table of n_chunks records the caller builds ONCE: every segment cut, in segment order, into pieces of at
+ * most GWD_HEALTH_CHUNK elements (every piece but a segment's last a multiple of 8 long), so that no piece straddles two
+ * segments; an empty segment has no piece.  One workgroup reduces one piece in a fixed order into partial[chunk]
+ * (gwd_query_workspace(GWD_WS_HEALTH, {n_chunks}) bytes, fully overwritten); a second launch folds the pieces of every segment in
+ * ascending chunk order.  No atomics, no memset: out is bit-identical from call to call.  16-byte loads; a piece's last
+ * len % 4 elements are read one by one.  -1 on a null pointer, S < 1 or n_chunks < 0; -3 when x is not 16-byte aligned.
+ *
+ * gwd_health_decide (one wave): folds the S records in segment order and fills the 64-byte control block:
+ *   sq = the fold of sumsq; nonfinite_total; apply = (nonfinite_total == 0); then applied += apply, skipped += !apply,
+ *   streak = apply ? 0 : streak + 1; when apply, bc1 / bc2 = fp32(1 - beta^t), t = applied (after the increment), computed in
+ *   fp64 and rounded once; clip_coef = min(max_norm / (fp32(sqrt(sq)) * grad_scale + 1e-6), 1) as gwd_adamw_step forms it (1
+ *   when max_norm <= 0).  `loss` (DEVICE fp32, may be NULL: recorded as 0 / not finite = 0) is recorded and never decides.
+ *   ring[(step - 1) % ring_len] = the step's record, step = applied + skipped (after the increments).  When the step is NOT
+ *   applied, bad[s] = out[s].nonfinite for every segment (bad keeps the culprits of the last skipped step).
+ *   -1 on a null pointer (loss excepted), S < 1 or ring_len < 1.
+ *
+ * gwd_adamw_step_guarded: gwd_adamw_step with sq, bias_corr1 and bias_corr2 read from `ctl`; stores nothing when
+ * ctl->apply == 0.                                                                                                              */
+#define GWD_HEALTH_CHUNK 16384
+typedef struct {
+    double sumsq;
+    float absmax;
+    int32_t nonfinite;
+} gwd_segment_record;
+typedef struct {
+    int64_t begin;      /* first element of the piece in x */
+    int32_t len;        /* 1 .. GWD_HEALTH_CHUNK */
+    int32_t segment;
+} gwd_health_chunk;
+typedef struct {
+    double sq;
+    int64_t applied, skipped, streak;
+    int32_t nonfinite_total, apply, loss_finite, reserved;
+    float bc1, bc2, clip_coef, loss;
+} gwd_health_ctl;       /* 64 bytes; all zero before the first step (applied may be seeded from a checkpoint) */
+typedef struct {
+    int64_t step;       /* 1-based; 0 = slot never written */
+    double grad_norm;   /* sqrt(sq) * grad_scale, over the finite elements */
+    float clip_coef, loss;
+    int32_t apply, nonfinite_total;
+} gwd_health_record;    /* 32 bytes */
+int gwd_segment_stats(const float *x, const int64_t *seg_begin, const int64_t *seg_end, int32_t S, const gwd_health_chunk *chunks,
+                      int32_t n_chunks, void *partial, gwd_segment_record *out, void *stream);
+int gwd_health_decide(const gwd_segment_record *stats, int32_t S, const float *loss, gwd_health_ctl *ctl, gwd_health_record *ring,
+                      int32_t ring_len, int32_t *bad, double beta1, double beta2, float max_norm, float grad_scale, void *stream);
+int gwd_adamw_step_guarded(float *p, const float *g, float *m, float *v, void *p_bf16, const gwd_health_ctl *ctl, int64_t n,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                           void *stream);
 
 #ifdef __cplusplus
 }
