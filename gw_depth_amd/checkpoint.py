@@ -157,9 +157,14 @@ def save_checkpoint(path, model, optimizer, lr_scheduler, epoch, args=None):
     osd = optimizer.state_dict()
     osd["state"] = {k: {kk: (vv.detach().cpu().clone() if torch.is_tensor(vv) else vv) for kk, vv in v.items()}
                     for k, v in osd["state"].items()}
-    torch.save({"model": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "optimizer": osd,
-                "lr_scheduler": lr_scheduler.state_dict() if lr_scheduler is not None else None, "epoch": epoch,
-                "args": args}, path)
+    ckpt = {"model": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "optimizer": osd,
+            "lr_scheduler": lr_scheduler.state_dict() if lr_scheduler is not None else None, "epoch": epoch,
+            "args": args}
+    ts = getattr(optimizer, "ts", None)
+    if ts is not None and ts.flat_e is not None:               # the weight average: the model's own keys and layouts, and its update count
+        ckpt["model_ema"] = {k: v.cpu() for k, v in ts.ema_state_dict().items()}
+        ckpt["ema_updates"] = int(ts.ema_updates())
+    torch.save(ckpt, path)
 
 
 def load_checkpoint(checkpoint, model, optimizer=None, lr_scheduler=None, args=None, log=print):
@@ -183,5 +188,21 @@ def load_checkpoint(checkpoint, model, optimizer=None, lr_scheduler=None, args=N
         if args is not None and hasattr(args, "lr_drop"):
             lrs["step_size"] = args.lr_drop                     # :159 "change the lr_drop epoch"
         lr_scheduler.load_state_dict(lrs)
+        _load_ema(checkpoint, model, ts, log, no_opt)
         return checkpoint["epoch"] + 1
+    _load_ema(checkpoint, model, ts, log, no_opt)
     return None
+
+
+def _load_ema(checkpoint, model, ts, log, no_opt):
+    """The weight average of a TrainStep(ema_decay=...): from "model_ema" (the values land in flat_e, the update count continues
+    from "ema_updates"); without the key, or with --no_opt / --eval, seeded from the loaded weights.  A step without EMA ignores
+    the key."""
+    if ts is None or ts.flat_e is None:
+        return
+    if not no_opt and checkpoint.get("model_ema") is not None:
+        with ts.use_ema():
+            model.load_state_dict(remap_resume_state_dict(checkpoint["model_ema"], log), strict=False)
+        ts.ema_t0 = ts.applied_steps() - int(checkpoint.get("ema_updates", 0))
+    else:
+        ts.reset_ema()

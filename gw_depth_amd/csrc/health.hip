@@ -2,6 +2,7 @@
 // magnitude, number of non-finite elements), the decision whether the step is applied, and AdamW reading that decision.
 // One streaming pass over the buffer (the pass sqnorm_kernel makes), no atomics, no memset: every sum has one fixed order.
 #include "common.h"
+#include "adamw.h"
 
 namespace {
 
@@ -200,25 +201,18 @@ __global__ __launch_bounds__(64) void health_decide_kernel(const gwd_segment_rec
     ring[(r.step - 1) % ring_len] = r;
 }
 
-// adamw_kernel of optim.hip, statement for statement, with sq / bc1 / bc2 read from the control block
+// adamw_kernel of optim.hip (the same two functions of adamw.h), with sq / bc1 / bc2 read from the control block
 __global__ __launch_bounds__(256) void adamw_guarded_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                             float *__restrict__ v, __bf16 *__restrict__ p16,
                                                             const gwd_health_ctl *__restrict__ ctl, int64_t n, float lr, float b1, float b2,
                                                             float eps, float wd, float max_norm, float grad_scale) {
     if (ctl->apply == 0) return;
     const float bc1 = ctl->bc1, bc2 = ctl->bc2;
-    float coef = grad_scale;
-    if (max_norm > 0.f) {
-        const float total = (float)sqrt(ctl->sq) * grad_scale;
-        coef *= fminf(max_norm / (total + 1e-6f), 1.0f);
-    }
+    const float coef = adamw_coef(&ctl->sq, max_norm, grad_scale);
     const float step = lr / bc1, rs2 = rsqrtf(bc2);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = g[i] * coef;
-        float pi = p[i] * (1.0f - lr * wd);
-        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
-        const float vi = v[i] * b2 + gi * gi * (1.0f - b2);
-        pi -= step * mi / (sqrtf(vi) * rs2 + eps);
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_element(pi, g[i], mi, vi, coef, lr, b1, b2, eps, wd, step, rs2);
         p[i] = pi;
         m[i] = mi;
         v[i] = vi;

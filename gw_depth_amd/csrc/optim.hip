@@ -1,6 +1,7 @@
 // Flat-buffer optimizer step: global gradient norm, clip and AdamW in two streaming passes over the
 // 66 M trainable elements (4 reads + 3 writes of fp32 per element + an optional bf16 shadow write).
 #include "common.h"
+#include "adamw.h"
 
 namespace {
 
@@ -28,19 +29,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float *__restrict__ p, const
                                                     const double *__restrict__ sq, int64_t n, float lr, float b1, float b2,
                                                     float eps, float wd, float bc1, float bc2, float max_norm,
                                                     float grad_scale) {
-    float coef = grad_scale;
-    if (sq && max_norm > 0.f) {
-        // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
-        const float total = (float)sqrt(sq[0]) * grad_scale;
-        coef *= fminf(max_norm / (total + 1e-6f), 1.0f);
-    }
+    const float coef = adamw_coef(sq, max_norm, grad_scale);
     const float step = lr / bc1, rs2 = rsqrtf(bc2);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = g[i] * coef;
-        float pi = p[i] * (1.0f - lr * wd);
-        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);     // lerp, as torch's exp_avg.lerp_
-        const float vi = v[i] * b2 + gi * gi * (1.0f - b2);
-        pi -= step * mi / (sqrtf(vi) * rs2 + eps);
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_element(pi, g[i], mi, vi, coef, lr, b1, b2, eps, wd, step, rs2);
         p[i] = pi;
         m[i] = mi;
         v[i] = vi;

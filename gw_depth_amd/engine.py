@@ -18,6 +18,7 @@ optimizer / DDP setup of /root/reference/src/main_glassrgbd.py:46-67, re-laid fo
   boundaries: after graph k has been enqueued its buckets go to the communication stream while graph
   k+1 runs, so the gradient all-reduce overlaps with backward in the replayed step as well.
 """
+import contextlib
 import gc
 import math
 import os
@@ -110,9 +111,16 @@ def _align(n):
 class TrainStep:
     def __init__(self, model, criterions, cfg, compute_dtype=torch.float32, bucket_mb=32.0, process_group=None,
                  check_finite=True, data_parallel=True, graph=False, segments=None, max_graphs=None, capture_after=1,
-                 guard="off", stats_every=0, ring=64, max_consecutive_skips=8):
+                 guard="off", stats_every=0, ring=64, max_consecutive_skips=8, ema_decay=None, ema_warmup=True):
         if guard not in ("off", "skip"):
             raise ValueError("guard must be 'off' or 'skip', got %r" % (guard,))
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must be None or lie in (0, 1), got %r" % (ema_decay,))
+        # fp32 average of the master weights, updated inside the AdamW pass; None: nothing is allocated
+        self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
+        self.flat_e = None
+        self.ema_t0 = 0                   # applied optimizer steps when averaging began: update number t = applied steps - ema_t0
+        self._in_ema = False              # inside use_ema(): flat_p holds the average, flat_e the weights
         if int(stats_every) < 0 or int(max_consecutive_skips) < 0:
             raise ValueError("stats_every and max_consecutive_skips must be >= 0")
         self.guard, self.stats_every, self.max_consecutive_skips = guard, int(stats_every), int(max_consecutive_skips)
@@ -184,6 +192,8 @@ class TrainStep:
             self._broadcast_from_rank0()
         if self.flat_p16 is not None:
             self.flat_p16.copy_(self.flat_p)
+        if self.ema_decay is not None:
+            self.flat_e = self.flat_p.clone()              # after the broadcast: every rank averages the same weights, no collective
         spans = [(self.flat_p.data_ptr(), self.flat_p.data_ptr() + self.flat_p.numel() * 4)]
         spans += [(p.data_ptr(), p.data_ptr() + p.numel() * p.element_size()) for p in model.parameters() if not p.requires_grad]
         self.weights = ops.WeightCache(spans)
@@ -392,6 +402,7 @@ class TrainStep:
     def optimizer_step(self, loss=None):
         """Clip + AdamW on the flat buffers.  guard="skip": per-tensor statistics of flat_g, the decision on the device, then AdamW
         that stores nothing when a gradient element is not finite; `loss` (a device scalar, optional) is recorded, it never decides."""
+        self._not_in_ema("optimizer_step")
         cfg, lib = self.cfg, hip.library()
         self.step_count += 1
         gs = 1.0 / self.world
@@ -405,6 +416,12 @@ class TrainStep:
             hs.grad_stats(lib, self.flat_g)
             hs.decide(lib, None if loss is None else loss.detach().reshape(1).float(), 0.9, 0.999, cfg.clip_max_norm, gs)
             for lo, hi, lr in groups:
+                if self.flat_e is not None:         # the device's own apply / skip decision holds for the average too
+                    lib.adamw_step_ema(self.flat_p[lo:hi], self.flat_g[lo:hi], self.flat_m[lo:hi], self.flat_v[lo:hi],
+                                       None if self.flat_p16 is None else self.flat_p16[lo:hi], self.flat_e[lo:hi], None, hs.ctl,
+                                       hi - lo, lr, 0.9, 0.999, 1e-8, cfg.weight_decay, 1.0, 1.0, cfg.clip_max_norm, gs,
+                                       self.ema_decay, self.ema_warmup, self.ema_t0)
+                    continue
                 lib.adamw_step_guarded(self.flat_p[lo:hi], self.flat_g[lo:hi], self.flat_m[lo:hi], self.flat_v[lo:hi],
                                        None if self.flat_p16 is None else self.flat_p16[lo:hi], hs.ctl, hi - lo, lr, 0.9, 0.999,
                                        1e-8, cfg.weight_decay, cfg.clip_max_norm, gs)
@@ -416,6 +433,12 @@ class TrainStep:
             self.sq.zero_()
             lib.sqnorm(self.flat_g, self.sq, self.total)
             for lo, hi, lr in groups:
+                if self.flat_e is not None:
+                    lib.adamw_step_ema(self.flat_p[lo:hi], self.flat_g[lo:hi], self.flat_m[lo:hi], self.flat_v[lo:hi],
+                                       None if self.flat_p16 is None else self.flat_p16[lo:hi], self.flat_e[lo:hi], self.sq, None,
+                                       hi - lo, lr, 0.9, 0.999, 1e-8, cfg.weight_decay, bc1, bc2, cfg.clip_max_norm, gs,
+                                       self.ema_decay, self.ema_warmup, self.step_count - self.ema_t0)
+                    continue
                 lib.adamw_step(self.flat_p[lo:hi], self.flat_g[lo:hi], self.flat_m[lo:hi], self.flat_v[lo:hi],
                                None if self.flat_p16 is None else self.flat_p16[lo:hi], self.sq, hi - lo, lr, 0.9, 0.999,
                                1e-8, cfg.weight_decay, bc1, bc2, cfg.clip_max_norm, gs)
@@ -430,6 +453,53 @@ class TrainStep:
         if self.guard == "skip":
             return math.sqrt(self._health.read_ctl()["sq"]) / self.world
         return math.sqrt(float(self.sq.item())) / self.world
+
+    # ------------------------------------------------------------------ the weight average (ema_decay=...)
+    def _need_ema(self, what):
+        if self.flat_e is None:
+            raise RuntimeError("%s needs TrainStep(ema_decay=...)" % what)
+
+    def _not_in_ema(self, what):
+        if self._in_ema:
+            raise RuntimeError("%s inside use_ema(): the parameters hold the averaged weights; leave the block first" % what)
+
+    def _swap_ema(self):
+        hip.library().ema_swap(self.flat_p, self.flat_e, self.flat_p16, self.total)
+
+    @contextlib.contextmanager
+    def use_ema(self):
+        """Inside the block the model (so evaluate(), evaluate_frames() and an InferenceSession built there) runs on the averaged weights:
+        flat_p and flat_e exchange their CONTENTS in one launch and the bf16 shadow follows; no address moves, so captured graphs and
+        weight caches stay valid.  The exit swaps back, on exceptions too.  Does not nest; a train step inside raises."""
+        self._need_ema("use_ema()")
+        if self._in_ema:
+            raise RuntimeError("use_ema() does not nest")
+        self._swap_ema()
+        self._in_ema = True
+        self.model._gwd_ema_step = self               # an InferenceSession built now freezes these values (infer.py)
+        try:
+            yield self
+        finally:
+            self.model._gwd_ema_step = None
+            self._in_ema = False
+            self._swap_ema()
+
+    def ema_state_dict(self):
+        """model.state_dict() of the averaged weights (clones): the reference's key names and layouts."""
+        with self.use_ema():
+            return {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+
+    def reset_ema(self):
+        """Reseed the average from the current weights and restart the warm-up."""
+        self._need_ema("reset_ema()")
+        self._not_in_ema("reset_ema()")
+        self.flat_e.copy_(self.flat_p)
+        self.ema_t0 = self.applied_steps()
+
+    def ema_updates(self):
+        """Updates the average has taken (skipped steps do not count; one D2H copy with the guard on)."""
+        self._need_ema("ema_updates()")
+        return self.applied_steps() - self.ema_t0
 
     # ------------------------------------------------------------------ read-backs of the guarded step: one D2H copy each
     def _need_health(self, what, guard=True):
@@ -486,6 +556,7 @@ class TrainStep:
 
     def forward_backward(self, batch, taps=None):
         """Forward, losses, backward and (N > 1) the bucketed gradient all-reduce; leaves SUMMED grads in flat_g."""
+        self._not_in_ema("forward_backward")
         self.model.train()
         packed = self._packed(batch["targets"]) if self.device_matcher else None
         if packed is None:
@@ -679,6 +750,7 @@ class TrainStep:
 
     def __call__(self, batch, taps=None):
         """batch: dict(images (B,3,H,W), pad_mask (B,H,W) bool, depth (B,1,H,W), seg (B,1,H,W) i64, targets)."""
+        self._not_in_ema("a train step")
         if self.use_graph and batch["images"].is_cuda:
             if taps is not None:
                 self._cache.count("eager_steps")

@@ -42,6 +42,7 @@ ENTRY_POINTS = [
     "gwd_line_nms",
     "gwd_eval_frames",
     "gwd_segment_stats", "gwd_health_decide", "gwd_adamw_step_guarded",
+    "gwd_adamw_step_ema", "gwd_ema_swap",
 ]
 
 
@@ -122,6 +123,7 @@ EVAL_FRAMES_MAX_BINS = 8
 EVAL_FRAMES_WS_BYTES = 128 + 16 * 256 * 32 + 16 * 5 * 256 * 160      # GWD_EVAL_FRAMES_WS_BYTES; the first 128 bytes start as zeros
 HEALTH_CHUNK = 16384      # GWD_HEALTH_CHUNK: elements per piece of gwd_segment_stats
 HEALTH_RECORD_BYTES, HEALTH_CTL_BYTES, HEALTH_RING_BYTES = 16, 64, 32      # gwd_segment_record / gwd_health_chunk, gwd_health_ctl, gwd_health_record
+EMA_PASS = 1024 * 256 * 2 * 4        # GWD_EMA_PASS: elements per grid-stride pass of gwd_adamw_step_ema / gwd_ema_swap
 WIDEN_BATCH = 16          # gwd_widen_u16_batch jobs: the depth planes of one batch
 AUGMENT_BATCH = 16        # frames per grouped augmentation launch
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
@@ -306,6 +308,8 @@ class HipLibrary:
         L.gwd_segment_stats.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp]
         L.gwd_health_decide.argtypes = [vp, i32, vp, vp, vp, i32, vp, ctypes.c_double, ctypes.c_double, f32, f32, vp]
         L.gwd_adamw_step_guarded.argtypes = [vp, vp, vp, vp, vp, vp, i64] + [f32] * 7 + [vp]
+        L.gwd_adamw_step_ema.argtypes = [vp] * 8 + [i64] + [f32] * 9 + [ctypes.c_double, i32, i64, vp]
+        L.gwd_ema_swap.argtypes = [vp, vp, vp, i64, vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1227,6 +1231,29 @@ class HipLibrary:
         self._check(self.lib.gwd_adamw_step_guarded(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(p16), _ptr(ctl), n, lr, b1, b2, eps, wd,
                                                     max_norm, grad_scale, self._stream(p, g, m, v, ctl)),
                     "gwd_adamw_step_guarded")
+
+    def adamw_step_ema(self, p, g, m, v, p16, ema, sq, ctl, n, lr, b1, b2, eps, wd, bc1, bc2, max_norm, grad_scale, ema_decay, ema_warmup,
+                       ema_t):
+        """gwd_adamw_step_ema.  ctl None: the step of adamw_step (sq may be None), ema_t the 1-based update number; ctl (uint8, 64
+        bytes): the step of adamw_step_guarded (sq, bc1, bc2 ignored), ema_t the applied-step count at which averaging began."""
+        if ctl is not None:
+            self._check_bytes(ctl, HEALTH_CTL_BYTES, "adamw_step_ema: ctl")
+        if any(t.dtype != torch.float32 or t.numel() < n for t in (p, g, m, v, ema)) or \
+                (p16 is not None and (p16.dtype != torch.bfloat16 or p16.numel() < n)):
+            raise ValueError("adamw_step_ema: p, g, m, v, ema are float32 (p16 bfloat16) ranges of at least n elements")
+        if sq is not None and (sq.dtype != torch.float64 or sq.numel() < 1):
+            raise TypeError("adamw_step_ema: sq is one float64 value on the device, or None")
+        if not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError("adamw_step_ema: ema_decay must lie in (0, 1), got %r" % (ema_decay,))
+        self._check(self.lib.gwd_adamw_step_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(p16), _ptr(ema), _ptr(sq), _ptr(ctl), n, lr, b1, b2,
+                                                eps, wd, bc1, bc2, max_norm, grad_scale, float(ema_decay), int(bool(ema_warmup)), int(ema_t),
+                                                self._stream(p, g, m, v, ema, ctl)), "gwd_adamw_step_ema")
+
+    def ema_swap(self, p, ema, p16, n):
+        """gwd_ema_swap: p <-> ema in place over n elements, p16 (or None) = bf16(new p)."""
+        if any(t.dtype != torch.float32 or t.numel() < n for t in (p, ema)) or (p16 is not None and (p16.dtype != torch.bfloat16 or p16.numel() < n)):
+            raise ValueError("ema_swap: p and ema are float32 (p16 bfloat16) ranges of at least n elements")
+        self._check(self.lib.gwd_ema_swap(_ptr(p), _ptr(ema), _ptr(p16), n, self._stream(p, ema)), "gwd_ema_swap")
 
 
 _LIB = None

@@ -61,6 +61,8 @@ class InferenceSession:
     by address) stay valid.  The cache is keyed by address: parameter storage must not move after the session is built -
     TrainStep.__init__ moves every parameter into its flat buffer, so build the session AFTER the TrainStep; refresh() checks
     and raises.  compute_dtype=torch.float32 has no copies to freeze (the kernels read the parameters themselves).
+    A session built inside TrainStep.use_ema() keeps the averaged weights after that block has ended: it clones the flat parameter
+    buffer and runs on the clone (every parameter, not only the matrices behind the frozen copies); refresh() re-clones.
 
     sess.predict_frames(frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False): decoded uint8 (h,w,3) camera
     frames in, the same results at every frame's OWN size out (see the method).
@@ -96,6 +98,13 @@ class InferenceSession:
         self._gstream = None
         self._addr = self._addresses()
         spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in self._storage() if t.numel()]
+        # built inside TrainStep.use_ema(): the averaged weights leave the parameters when that block ends, so the session keeps a copy
+        # of the flat buffer and runs every forward on it (biases and norms are read in place, not through the frozen copies)
+        ts = getattr(model, "_gwd_ema_step", None)
+        self._own = None if ts is None else (ts, ts.flat_p.clone())
+        if self._own is not None:
+            flat = self._own[1]
+            spans.append((flat.data_ptr(), flat.data_ptr() + flat.numel() * flat.element_size()))
         self.weights = ops.WeightCache(spans, frozen=True) if compute_dtype == torch.bfloat16 else None
 
     # ------------------------------------------------------------------ the reference passes `model`
@@ -124,13 +133,34 @@ class InferenceSession:
         if self._addresses() != self._addr:
             raise RuntimeError("gw_depth_amd: parameter storage moved after the InferenceSession was built (a TrainStep built "
                                "later moves every parameter into its flat buffer; model.to() re-allocates): build a new session")
-        with torch.no_grad(), self._on_stream():
+        if self._own is not None:                          # a session with its own weights takes what the parameters hold now
+            self._own[1].copy_(self._own[0].flat_p)
+        with torch.no_grad(), self._on_stream(), self._own_weights():
             for m in self.model.modules():
                 if hasattr(m, "folded"):
                     m.folded()
             if self.weights is not None:
                 self.weights.refresh()
         return self
+
+    @contextlib.contextmanager
+    def _own_weights(self):
+        """A session built inside TrainStep.use_ema(): for the length of a forward every trainable parameter is a view of the session's
+        own copy of the flat buffer (host-side pointer moves only: nothing is launched, a captured graph keeps the copy's addresses)."""
+        if self._own is None:
+            yield
+            return
+        ts, flat = self._own
+        keep = []
+        try:
+            for n, p in ts.params.items():
+                keep.append((p, p.data))
+                o = ts.offsets[n]
+                p.data = flat[o:o + p.numel()].view(p.shape)
+            yield
+        finally:
+            for p, d in keep:
+                p.data = d
 
     # ------------------------------------------------------------------ one sync-free pass
     def _forward(self, images, mask, taps=None):
@@ -143,7 +173,7 @@ class InferenceSession:
         if weights is not None:
             weights.begin_pass()
         try:
-            with torch.no_grad():
+            with torch.no_grad(), self._own_weights():
                 return model(NestedTensor(images, mask), taps=taps)
         finally:
             if weights is not None:

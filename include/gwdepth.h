@@ -895,6 +895,28 @@ int gwd_adamw_step_guarded(float *p, const float *g, float *m, float *v, void *p
                            float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
                            void *stream);
 
+/* Weight EMA fused into the AdamW pass (csrc/ema.hip).
+ *
+ * gwd_adamw_step_ema: the AdamW step of gwd_adamw_step (ctl == NULL: sq, which may be NULL, bias_corr1 and bias_corr2 as there) or of
+ *   gwd_adamw_step_guarded (ctl != NULL: sq, bc1 and bc2 from the control block, the three arguments ignored; nothing is stored, ema
+ *   included, when ctl->apply == 0) - p, m, v and the bf16 shadow come out bit-identical to those entry points - and, in the same
+ *   pass, the fp32 average of the NEW parameters:
+ *       ema' = fmaf(omd, p' - ema, ema),  omd = (float)(1 - d),  d = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay
+ *   with d formed in fp64 on the device and t the 1-based update number: t = ema_t (ctl == NULL) or ctl->applied - ema_t (ema_t =
+ *   the applied-step count at which averaging began).  A parameter that does not move keeps its average bit for bit.
+ *   Any 4-byte aligned fp32 range works; p, g, m, v and ema share their offset from a 16-byte boundary and p_bf16 sits at the same
+ *   ELEMENT offset from an 8-byte boundary (slices of flat buffers at equal offsets): -3 otherwise.  One grid-stride pass covers
+ *   GWD_EMA_PASS elements.  -1 on a null p, g, m, v or ema, n < 0 or ema_decay outside (0, 1); 0 at n == 0.
+ *
+ * gwd_ema_swap: exchanges p[i] and ema[i] in place; p_bf16 (may be NULL) becomes bf16(new p[i]) in the same pass.  Two calls restore
+ *   every bit of all three buffers.  Same alignment rule and return codes.                                                       */
+#define GWD_EMA_PASS 2097152
+int gwd_adamw_step_ema(float *p, const float *g, float *m, float *v, void *p_bf16, float *ema, const double *sq,
+                       const gwd_health_ctl *ctl, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       float bias_corr1, float bias_corr2, float max_norm, float grad_scale, double ema_decay, int32_t ema_warmup,
+                       int64_t ema_t, void *stream);
+int gwd_ema_swap(float *p, float *ema, void *p_bf16, int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
