@@ -7,6 +7,7 @@
 // line_post_kernel     PostProcess_Line 'prediction' (src/models/glassrgbd.py:470-477) for two classes, plus the queries ordered by
 //                      score (descending, equal scores by lower index) and the number of scores above a threshold.
 #include "common.h"
+#include "depthmm.h"          // to_mm: metres -> the PNGs' millimetres
 
 namespace {
 
@@ -33,11 +34,6 @@ __device__ __forceinline__ float clamp_depth(float p, float dmin, float dmax) {
     if (p > dmax) p = dmax;
     if (p != p) p = dmin;
     return p;
-}
-// rint(metres * 1000) as the PNGs hold it, saturated to the uint16 range
-__device__ __forceinline__ unsigned short to_mm(float d) {
-    const float mm = rintf(d * 1000.0f);
-    return (unsigned short)fminf(fmaxf(mm, 0.0f), 65535.0f);
 }
 // torch.argmax over (l0, l1): the first maximum wins, a NaN counts as the maximum
 __device__ __forceinline__ int argmax2(float l0, float l1) { return (l1 > l0 || (l1 != l1 && l0 == l0)) ? 1 : 0; }

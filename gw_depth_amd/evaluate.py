@@ -370,11 +370,16 @@ class FrameMetrics:
 
 @torch.no_grad()
 def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size=1024, max_size=1024, pad_to=None, depth_bins=None,
-                    metrics=None):
+                    metrics=None, planar=False):
     """Scores the samples `indices` (default: all) of a dataset.FrameStore / StreamSource through session.predict_frames at the
     frames' own resolution: `batch` frames per call (at most 16, 8 with ensemble=True), one gwd_eval_frames launch behind each,
     no host sync before the closing copy.  A device-resident FrameStore hands its 16-bit depth planes over in place (record_gt).
+    planar=True (a session built with regions= and its planar depth): the metrics are fed depth_planar - the depth with every fitted
+    glass region projected onto its plane in inverse depth, the prior GW-Depth's ground truth on glass was built with - in place of
+    depth; compare the glass rows of both runs.  Pixels outside the kept regions are the same in both.
     -> metrics.compute() plus "names": {sample index: name} for FrameMetrics.worst.  Pass `metrics` to keep the accumulator."""
+    if planar and not (getattr(session, "regions", None) or {}).get("planar"):
+        raise ValueError("evaluate_frames(planar=True) needs an InferenceSession built with regions= (and planar=True in it)")
     indices = list(range(len(source))) if indices is None else [int(i) for i in indices]
     limit = hip.EVAL_FRAMES_BATCH // 2 if ensemble else hip.EVAL_FRAMES_BATCH
     if not 0 < int(batch) <= limit:
@@ -391,6 +396,8 @@ def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size
             frames = source.frames(idx)
             rgb, gt = [f[0] for f in frames], [(f[1], f[2]) for f in frames]
         res = session.predict_frames(rgb, size=size, max_size=max_size, ensemble=ensemble, pad_to=pad_to)
+        if planar:
+            res = dict(res, depth=res["depth_planar"])
         metrics.update(res, gt, ids=idx)
     out = metrics.compute()
     out["names"] = {i: source.name(i) for i in indices}

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GWD_LIB") or os.path.join(_HERE, "libgwdepth_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3, 4
-WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH = 0, 1, 2, 3, 4          # gwd_query_workspace ops
+WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS = 0, 1, 2, 3, 4, 5          # gwd_query_workspace ops
 GATHER_CONV, GATHER_TRANSPOSED, GATHER_UPSAMPLED = 0, 1, 2
 RESAMPLE_BILINEAR_AC, RESAMPLE_NEAREST = 0, 1
 
@@ -43,6 +43,7 @@ ENTRY_POINTS = [
     "gwd_eval_frames",
     "gwd_segment_stats", "gwd_health_decide", "gwd_adamw_step_guarded",
     "gwd_adamw_step_ema", "gwd_ema_swap",
+    "gwd_glass_regions", "gwd_region_planes", "gwd_depth_planar",
 ]
 
 
@@ -126,6 +127,9 @@ HEALTH_RECORD_BYTES, HEALTH_CTL_BYTES, HEALTH_RING_BYTES = 16, 64, 32      # gwd
 EMA_PASS = 1024 * 256 * 2 * 4        # GWD_EMA_PASS: elements per grid-stride pass of gwd_adamw_step_ema / gwd_ema_swap
 WIDEN_BATCH = 16          # gwd_widen_u16_batch jobs: the depth planes of one batch
 AUGMENT_BATCH = 16        # frames per grouped augmentation launch
+REGION_MAX = 32           # GWD_REGION_MAX: kept regions per image, at most
+REGION_RECORD = 12        # GWD_REGION_RECORD: int64 fields of a region's record
+REGION_CANDIDATES = 8192  # GWD_REGION_CANDIDATES: default length of the candidate list per image
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
 COLOR_ADJUST, COLOR_SUMS = 0, 1
 
@@ -310,6 +314,9 @@ class HipLibrary:
         L.gwd_adamw_step_guarded.argtypes = [vp, vp, vp, vp, vp, vp, i64] + [f32] * 7 + [vp]
         L.gwd_adamw_step_ema.argtypes = [vp] * 8 + [i64] + [f32] * 9 + [ctypes.c_double, i32, i64, vp]
         L.gwd_ema_swap.argtypes = [vp, vp, vp, i64, vp]
+        L.gwd_glass_regions.argtypes = [vp] * 3 + [i32] * 9 + [vp] * 6
+        L.gwd_region_planes.argtypes = [vp] * 5 + [i32] * 6 + [vp] * 3
+        L.gwd_depth_planar.argtypes = [vp] * 6 + [i32] * 4 + [f32, f32] + [vp] * 3
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1254,6 +1261,64 @@ class HipLibrary:
         if any(t.dtype != torch.float32 or t.numel() < n for t in (p, ema)) or (p16 is not None and (p16.dtype != torch.bfloat16 or p16.numel() < n)):
             raise ValueError("ema_swap: p and ema are float32 (p16 bfloat16) ranges of at least n elements")
         self._check(self.lib.gwd_ema_swap(_ptr(p), _ptr(ema), _ptr(p16), n, self._stream(p, ema)), "gwd_ema_swap")
+
+    @staticmethod
+    def _typed(what, pairs):
+        for t, dt in pairs:
+            if t is not None and t.dtype != dt:
+                raise TypeError("%s: expected %s, got %s" % (what, dt, t.dtype))
+
+    def glass_regions(self, labels, depth_mm, sizes, max_regions, min_area, connectivity, max_candidates, lo_mm, hi_mm, workspace,
+                      region_map, region_count, region_total, records):
+        """gwd_glass_regions: labels uint8 / depth_mm uint16 (B,Fh,Fw), sizes (B,2) int32; outputs region_map uint8 (B,Fh,Fw),
+        region_count / region_total (B,) int32, records (B,max_regions,12) int64; workspace: a uint8 tensor of
+        workspace_bytes(WS_REGIONS, B, Fh, Fw, max_candidates) bytes."""
+        self._typed("gwd_glass_regions", ((labels, torch.uint8), (depth_mm, torch.uint16), (sizes, torch.int32), (workspace, torch.uint8),
+                                          (region_map, torch.uint8), (region_count, torch.int32), (region_total, torch.int32),
+                                          (records, torch.int64)))
+        B, Fh, Fw = labels.shape
+        if tuple(depth_mm.shape) != (B, Fh, Fw) or tuple(sizes.shape) != (B, 2) or tuple(region_map.shape) != (B, Fh, Fw) \
+                or region_count.numel() != B or region_total.numel() != B or tuple(records.shape) != (B, max_regions, REGION_RECORD) \
+                or workspace.numel() < self.workspace_bytes(WS_REGIONS, B, Fh, Fw, max_candidates):
+            raise ValueError("gwd_glass_regions: operand sizes do not match (B, Fh, Fw, max_regions) = (%d, %d, %d, %d)"
+                             % (B, Fh, Fw, max_regions))
+        self._check(self.lib.gwd_glass_regions(
+            _ptr(labels), _ptr(depth_mm), _ptr(sizes), B, Fh, Fw, int(max_regions), int(min_area), int(connectivity), int(max_candidates),
+            int(lo_mm), int(hi_mm), _ptr(workspace), _ptr(region_map), _ptr(region_count), _ptr(region_total), _ptr(records),
+            self._stream(labels, depth_mm, sizes, workspace, region_map, region_count, region_total, records)), "gwd_glass_regions")
+
+    def region_planes(self, region_map, depth_mm, sizes, region_count, records, lo_mm, hi_mm, workspace, planes):
+        """gwd_region_planes: the outputs and the workspace of glass_regions in, planes (B,max_regions,6) float64 out."""
+        self._typed("gwd_region_planes", ((region_map, torch.uint8), (depth_mm, torch.uint16), (sizes, torch.int32),
+                                          (region_count, torch.int32), (records, torch.int64), (workspace, torch.uint8),
+                                          (planes, torch.float64)))
+        B, Fh, Fw = region_map.shape
+        R = records.shape[1]
+        if tuple(depth_mm.shape) != (B, Fh, Fw) or tuple(sizes.shape) != (B, 2) or region_count.numel() != B \
+                or tuple(records.shape) != (B, R, REGION_RECORD) or tuple(planes.shape) != (B, R, 6) \
+                or workspace.numel() < self.workspace_bytes(WS_REGIONS, B, Fh, Fw, 1):
+            raise ValueError("gwd_region_planes: operand sizes do not match (B, Fh, Fw, max_regions) = (%d, %d, %d, %d)" % (B, Fh, Fw, R))
+        self._check(self.lib.gwd_region_planes(
+            _ptr(region_map), _ptr(depth_mm), _ptr(sizes), _ptr(region_count), _ptr(records), B, Fh, Fw, R, int(lo_mm), int(hi_mm),
+            _ptr(workspace), _ptr(planes), self._stream(region_map, depth_mm, sizes, region_count, records, workspace, planes)),
+            "gwd_region_planes")
+
+    def depth_planar(self, region_map, depth_mm, depth, sizes, region_count, planes, dmin, dmax, depth_planar, depth_planar_mm):
+        """gwd_depth_planar: depth (B,Fh,Fw) float32 or None (millimetres / 1000); outputs float32 / uint16 (B,Fh,Fw)."""
+        self._typed("gwd_depth_planar", ((region_map, torch.uint8), (depth_mm, torch.uint16), (depth, torch.float32), (sizes, torch.int32),
+                                         (region_count, torch.int32), (planes, torch.float64), (depth_planar, torch.float32),
+                                         (depth_planar_mm, torch.uint16)))
+        B, Fh, Fw = region_map.shape
+        R = planes.shape[1]
+        shape = (B, Fh, Fw)
+        if tuple(depth_mm.shape) != shape or (depth is not None and tuple(depth.shape) != shape) or tuple(sizes.shape) != (B, 2) \
+                or region_count.numel() != B or tuple(planes.shape) != (B, R, 6) or tuple(depth_planar.shape) != shape \
+                or tuple(depth_planar_mm.shape) != shape:
+            raise ValueError("gwd_depth_planar: operand sizes do not match (B, Fh, Fw, max_regions) = (%d, %d, %d, %d)" % (B, Fh, Fw, R))
+        self._check(self.lib.gwd_depth_planar(
+            _ptr(region_map), _ptr(depth_mm), _ptr(depth), _ptr(sizes), _ptr(region_count), _ptr(planes), B, Fh, Fw, R, float(dmin),
+            float(dmax), _ptr(depth_planar), _ptr(depth_planar_mm),
+            self._stream(region_map, depth_mm, depth, sizes, region_count, planes, depth_planar, depth_planar_mm)), "gwd_depth_planar")
 
 
 _LIB = None

@@ -24,6 +24,8 @@ from .model import NestedTensor, nested_tensor_from_tensor_list
 
 RESULT_KEYS = ("depth", "depth_mm", "labels", "scores", "lines", "order", "count", "sizes")
 NMS_KEYS = ("nms_lines", "nms_scores", "nms_ids", "nms_count")          # added to a result by a session built with line_nms=
+_REGION_OPTIONS = ("max_regions", "min_area", "connectivity", "min_depth", "max_depth", "planes", "planar", "max_candidates")
+REGION_KEYS = ops.REGION_KEYS                                          # added to predict_frames' result by a session built with regions=
 
 
 def _count_memsets_in(fn):
@@ -75,11 +77,18 @@ class InferenceSession:
     ("query"); line_nms_min_score=s lets only queries with score > s take part.  C = Q; with predict_frames(ensemble=True)
     the mirrored twin's queries, mirrored back, take part as well: C = 2 Q and ids >= Q name the twin's queries.
 
+    GLASS REGIONS.  regions=None (the default): nothing is allocated and predict_frames issues the launches and returns the keys it
+    always did.  regions=True or a dict of ops.glass_regions' keyword arguments (max_regions, min_area, connectivity, planes,
+    planar, max_candidates; min_depth / max_depth default to the session's): predict_frames also returns REGION_KEYS (those the
+    switches ask for, ops.region_keys) - the connected glass regions of every frame, their records, their planes in inverse depth
+    and the depth those planes predict - computed from its own labels / depth_mm / depth / sizes behind the resized
+    post-processing, on the session's stream, as fresh tensors, with no host sync.  predict() does not take part.
+
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
 
     def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6,
-                 line_nms=None, line_nms_order="score", line_nms_min_score=None):
+                 line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None):
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
         if line_nms_order not in ("score", "query"):
@@ -93,6 +102,12 @@ class InferenceSession:
         self.compute_dtype = compute_dtype
         self.use_graph = bool(graph)
         self.min_depth, self.max_depth, self.score_thresh = float(min_depth), float(max_depth), float(score_thresh)
+        if regions is not None and regions is not True and not isinstance(regions, dict):
+            raise TypeError("regions must be None, True or a dict of ops.glass_regions' keyword arguments, got %r" % (regions,))
+        if isinstance(regions, dict) and set(regions) - set(_REGION_OPTIONS):
+            raise TypeError("regions: unknown option(s) %s (known: %s)" % (sorted(set(regions) - set(_REGION_OPTIONS)), ", ".join(_REGION_OPTIONS)))
+        self.regions = None if regions is None else ops.check_region_options(
+            **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(regions if isinstance(regions, dict) else {})))
         self._graphs = OrderedDict()
         self._pool = None
         self._gstream = None
@@ -362,6 +377,8 @@ class InferenceSession:
         A session with line_nms adds NMS_KEYS in frame pixels; with ensemble=True the mirrored frames' queries, mirrored back,
         are candidates too (C = 2 Q rows per frame).  Without line_nms the twin's lines stay unused.
 
+        A session with regions= adds REGION_KEYS (GLASS REGIONS above), at frame size.
+
         -> RESULT_KEYS + "net_sizes": depth / depth_mm / labels (B, Fh, Fw) with (Fh, Fw) the largest frame of the call (outside
         a frame 0 / 0 / 255), sizes (B,2) the FRAME sizes, net_sizes (B,2) the un-padded network sizes, scores / lines / order /
         count as predict() gives them for the B frames, lines in frame pixels.  The dense results, sizes and net_sizes are fresh
@@ -394,7 +411,10 @@ class InferenceSession:
             depth, mm, labels = ops.dense_postprocess_resized(
                 raw["pred_depth"][-1], raw["pred_seg"], nsz, fsz, (max(s[0] for s in frame_sizes), max(s[1] for s in frame_sizes)),
                 self.min_depth, self.max_depth, twin=B if ensemble else 0)
+            regions = None if self.regions is None else ops.glass_regions(labels, mm, fsz, depth=depth, **self.regions)
         res = {"depth": depth, "depth_mm": mm, "labels": labels, "sizes": fsz, "net_sizes": nsz}
+        if regions is not None:
+            res.update(regions)
         for k in ("scores", "lines", "order", "count") + (NMS_KEYS if self.line_nms is not None else ()):
             res[k] = post[k][:B].clone() if copy else post[k][:B]
         return res

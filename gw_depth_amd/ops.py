@@ -2164,3 +2164,94 @@ def line_nms(logits, lines, sizes, threshold, order=None, min_score=None, twin=0
     nms_count = torch.empty((B,), dtype=torch.int32, device=dev)
     _lib().line_nms(logits, lines, sizes, order, threshold, min_score, nms_lines, nms_scores, nms_ids, nms_count, twin)
     return nms_lines, nms_scores, nms_ids, nms_count
+
+
+REGION_KEYS = ("region_map", "region_count", "region_total", "regions", "planes", "depth_planar", "depth_planar_mm")
+REGION_FIELDS = ("area", "x0", "y0", "x1", "y1", "anchor", "sum_x", "sum_y", "n_depth", "sum_mm", "min_mm", "max_mm")
+
+
+def region_keys(planes=True, planar=True):
+    """The keys glass_regions returns for these switches."""
+    return REGION_KEYS[:4] + (("planes",) if planes or planar else ()) + (REGION_KEYS[5:] if planar else ())
+
+
+def region_mm_range(min_depth, max_depth):
+    """The millimetres lo .. hi (inclusive) that lie in [min_depth, max_depth] metres: a region's pixels `with depth`."""
+    lo = max(1, -int(-(float(min_depth) * 1000.0 - 1e-6) // 1))
+    hi = min(65535, int((float(max_depth) * 1000.0 + 1e-6) // 1))
+    return lo, hi
+
+
+def check_region_options(max_regions=32, min_area=100, connectivity=8, min_depth=1e-3, max_depth=10.0, planes=True, planar=True,
+                         max_candidates=None):
+    """Host validation of glass_regions' options (also what InferenceSession(regions=...) accepts); -> them as a dict."""
+    if connectivity not in (4, 8):
+        raise ValueError("glass_regions: connectivity must be 4 or 8, got %r" % (connectivity,))
+    if not 1 <= int(max_regions) <= hip.REGION_MAX:
+        raise ValueError("glass_regions: 1 <= max_regions <= %d, got %r" % (hip.REGION_MAX, max_regions))
+    if int(min_area) < 1:
+        raise ValueError("glass_regions: min_area >= 1, got %r" % (min_area,))
+    max_candidates = hip.REGION_CANDIDATES if max_candidates is None else int(max_candidates)
+    if not 1 <= max_candidates <= 1 << 24:
+        raise ValueError("glass_regions: 1 <= max_candidates <= 2^24, got %r" % (max_candidates,))
+    if not 0.0 < float(min_depth) < float(max_depth):
+        raise ValueError("glass_regions: 0 < min_depth < max_depth, got %r, %r" % (min_depth, max_depth))
+    lo, hi = region_mm_range(min_depth, max_depth)
+    if lo > hi:
+        raise ValueError("glass_regions: no whole millimetre lies in [%r, %r] metres" % (min_depth, max_depth))
+    return dict(max_regions=int(max_regions), min_area=int(min_area), connectivity=int(connectivity), min_depth=float(min_depth),
+                max_depth=float(max_depth), planes=bool(planes), planar=bool(planar), max_candidates=max_candidates)
+
+
+def glass_regions(labels, depth_mm, sizes, max_regions=32, min_area=100, connectivity=8, min_depth=1e-3, max_depth=10.0, planes=True,
+                  planar=True, max_candidates=None, depth=None):
+    """From pixels to objects, on the device (gwd_glass_regions / gwd_region_planes / gwd_depth_planar):
+    labels (B,Fh,Fw) uint8 (1 = glass), depth_mm (B,Fh,Fw) uint16, sizes (B,2) int32 (fh, fw) on the device - what
+    InferenceSession.predict_frames returns; B <= 16, sides <= 16384.  A pixel outside its frame never takes part.
+
+    -> dict: region_map (B,Fh,Fw) uint8 (0 = in no kept region, r + 1 = rank r), region_count (B,) int32 (-1: more than
+    max_candidates components of min_area pixels or more, the image is refused), region_total (B,) int32 (components before
+    min_area), regions (B,max_regions,12) int64 in REGION_FIELDS order, rows from region_count on 0.  The kept regions are the
+    max_regions largest components (4- or 8-connected) of area >= min_area, ranked by (area descending, anchor ascending), anchor =
+    the smallest raster index y * fw + x of the component.  n_depth / sum_mm / min_mm / max_mm run over the pixels whose
+    millimetres lie in [min_depth, max_depth] metres.
+    planes=True: planes (B,max_regions,6) float64 = alpha, beta, gamma, rms, n_used, status: the least-squares plane
+    w = alpha x + beta y + gamma in inverse depth w = 1000 / depth_mm (1 / m) over those pixels; status 1 (NaN coefficients) for
+    fewer than 3 or collinear pixels.  With pinhole intrinsics (fx, fy, cx, cy) the 3-D plane n . P = d follows in closed form:
+    with m = (alpha fx, beta fy, gamma + alpha cx + beta cy), n = m / |m| and d = 1 / |m| (a point (X, Y, Z) projects to
+    x = fx X / Z + cx, y = fy Y / Z + cy, so n . P = d divided by d Z is affine in (x, y, 1 / Z)).
+    planar=True (implies the fit): depth_planar (B,Fh,Fw) float32 and depth_planar_mm uint16 = `depth` (float32, default
+    depth_mm / 1000) and depth_mm with every pixel of a fitted region where alpha x + beta y + gamma > 0 rewritten to
+    clamp(1 / (alpha x + beta y + gamma), min_depth, max_depth); outside the frames 0 / 0.
+    Fresh tensors, no host sync; repeated calls give bit-identical results."""
+    opt = check_region_options(max_regions, min_area, connectivity, min_depth, max_depth, planes, planar, max_candidates)
+    for name, t, dt in (("labels", labels, torch.uint8), ("depth_mm", depth_mm, torch.uint16), ("sizes", sizes, torch.int32),
+                        ("depth", depth, torch.float32)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dt):
+            raise TypeError("glass_regions: %s must be a %s tensor" % (name, dt))
+    if labels.dim() != 3 or 0 in labels.shape:
+        raise ValueError("glass_regions: labels must be (B, Fh, Fw), got %s" % (tuple(labels.shape),))
+    B, Fh, Fw = labels.shape
+    if B > hip.AUGMENT_BATCH or max(Fh, Fw) > 16384:
+        raise ValueError("glass_regions: at most %d frames of at most 16384 per side, got %s" % (hip.AUGMENT_BATCH, tuple(labels.shape)))
+    if tuple(depth_mm.shape) != (B, Fh, Fw) or tuple(sizes.shape) != (B, 2) or (depth is not None and tuple(depth.shape) != (B, Fh, Fw)):
+        raise ValueError("glass_regions: depth_mm / depth must be %s and sizes (%d, 2)" % ((B, Fh, Fw), B))
+    lib, dev, R = _lib(), labels.device, opt["max_regions"]
+    labels, depth_mm, sizes = labels.contiguous(), depth_mm.contiguous(), sizes.contiguous()
+    lo, hi = region_mm_range(opt["min_depth"], opt["max_depth"])
+    ws = torch.empty(lib.workspace_bytes(hip.WS_REGIONS, B, Fh, Fw, opt["max_candidates"]), dtype=torch.uint8, device=dev)
+    res = {"region_map": torch.empty((B, Fh, Fw), dtype=torch.uint8, device=dev),
+           "region_count": torch.empty((B,), dtype=torch.int32, device=dev),
+           "region_total": torch.empty((B,), dtype=torch.int32, device=dev),
+           "regions": torch.empty((B, R, hip.REGION_RECORD), dtype=torch.int64, device=dev)}
+    lib.glass_regions(labels, depth_mm, sizes, R, opt["min_area"], opt["connectivity"], opt["max_candidates"], lo, hi, ws,
+                      res["region_map"], res["region_count"], res["region_total"], res["regions"])
+    if opt["planes"] or opt["planar"]:
+        res["planes"] = torch.empty((B, R, 6), dtype=torch.float64, device=dev)
+        lib.region_planes(res["region_map"], depth_mm, sizes, res["region_count"], res["regions"], lo, hi, ws, res["planes"])
+    if opt["planar"]:
+        res["depth_planar"] = torch.empty((B, Fh, Fw), dtype=torch.float32, device=dev)
+        res["depth_planar_mm"] = torch.empty((B, Fh, Fw), dtype=torch.uint16, device=dev)
+        lib.depth_planar(res["region_map"], depth_mm, None if depth is None else depth.contiguous(), sizes, res["region_count"],
+                         res["planes"], opt["min_depth"], opt["max_depth"], res["depth_planar"], res["depth_planar_mm"])
+    return res

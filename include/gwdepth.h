@@ -88,8 +88,9 @@ const char *gwd_arch(void);
  *   GWD_WS_EVAL            dims = {B, H*W}         -> `workspace` of gwd_eval_accumulate
  *   GWD_WS_PLANE           dims = {P, H*W}         -> `workspace` of gwd_plane_loss_forward
  *   GWD_WS_HEALTH          dims = {n_chunks}       -> `partial` of gwd_segment_stats
+ *   GWD_WS_REGIONS         dims = {B, Fh, Fw, max_candidates} -> `workspace` of gwd_glass_regions / gwd_region_planes
  * Returns -1 for an unknown op or a wrong dimension count.                                                     */
-enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3, GWD_WS_HEALTH = 4 };
+enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3, GWD_WS_HEALTH = 4, GWD_WS_REGIONS = 5 };
 int64_t gwd_query_workspace(int32_t op, const int64_t *dims, int32_t ndims);
 
 /* Implicit-GEMM convolution on MFMA with fused epilogue y = act(scale*conv(x,w) + shift + residual).
@@ -916,6 +917,51 @@ int gwd_adamw_step_ema(float *p, const float *g, float *m, float *v, void *p_bf1
                        float bias_corr1, float bias_corr2, float max_norm, float grad_scale, double ema_decay, int32_t ema_warmup,
                        int64_t ema_t, void *stream);
 int gwd_ema_swap(float *p, float *ema, void *p_bf16, int64_t n, void *stream);
+
+/* Glass regions on the device (csrc/regions.hip): from the frame-size results of
+ * InferenceSession.predict_frames to objects.  labels [B][Fh][Fw] uint8 (1 = glass), depth_mm [B][Fh][Fw] uint16, sizes [B][2]
+ * int32 (fh, fw) on the DEVICE; frame b sits top-left in plane b and a pixel outside (fh, fw) never takes part, whatever byte it
+ * holds.  B <= 16, Fh, Fw <= 16384.  No host synchronisation, no memset, no floating-point atomics; no loop of any kernel waits
+ * for another thread.  workspace: gwd_query_workspace(GWD_WS_REGIONS, {B, Fh, Fw, max_candidates}) bytes, 16-byte aligned, needs no
+ * initialisation; calls that share it must be ordered on one stream, and gwd_region_planes takes the workspace (and B) of the
+ * gwd_glass_regions call whose outputs it reads.
+ *
+ * gwd_glass_regions: connected components of the glass pixels of every frame, `connectivity` 4 or 8 (union-find over an int32
+ *   parent plane; the representative - `anchor` - of a component is its smallest raster index y * fw + x in FRAME coordinates).
+ *   Components with area >= min_area are candidates; the max_regions (<= GWD_REGION_MAX) largest are kept, ranked by (area
+ *   descending, anchor ascending).  An image with more than max_candidates candidates is refused: region_count = -1, map and
+ *   records 0.  A pixel counts as having depth when lo_mm <= depth_mm <= hi_mm (1 <= lo_mm <= hi_mm <= 65535).
+ *     region_map   [B][Fh][Fw] uint8   0 = in no kept region (all of the plane outside the frame included), r + 1 = rank r
+ *     region_count [B] int32           kept regions, or -1
+ *     region_total [B] int32           components found, before min_area
+ *     records      [B][max_regions][GWD_REGION_RECORD] int64, rows from region_count on 0:
+ *                  area, x0, y0, x1, y1 (inclusive box), anchor, sum_x, sum_y, n_depth, sum_mm, min_mm, max_mm (the last three
+ *                  over the n_depth pixels with depth; 0 when there are none).  Exact.
+ * gwd_region_planes: per kept region the least-squares plane w = alpha x + beta y + gamma in inverse depth, w = 1000 / depth_mm
+ *   formed in fp64 (1 / m), x, y frame pixels, over its n_depth pixels.  For a pinhole camera (fx, fy, cx, cy) the 3-D plane
+ *   n . P = d maps to alpha = nx / (fx d), beta = ny / (fy d), gamma = (nz - nx cx / fx - ny cy / fy) / d, so no intrinsics are
+ *   needed to fit.  planes [B][max_regions][6] fp64: alpha, beta, gamma, rms of the residual w - fit (1 / m), n_used, status;
+ *   status 1 (coefficients and rms NaN): fewer than 3 pixels, or collinear pixels - decided exactly from the integer moments.
+ *   Rows from region_count on are 0.  Bit-identical from call to call.
+ * gwd_depth_planar: depth_planar fp32 / depth_planar_mm uint16 [B][Fh][Fw] = `depth` (fp32, may be NULL: depth_mm / 1000) and
+ *   depth_mm, with every pixel of a kept region of status 0 where alpha x + beta y + gamma > 0 rewritten to
+ *   clamp(1 / (alpha x + beta y + gamma), min_depth, max_depth), evaluated in fp64 and rounded once to fp32; its millimetres by
+ *   gwd_dense_postprocess's conversion.  Outside the frame 0 / 0.
+ * -1 on a null pointer or a size / count / range outside its limits, -2 when connectivity is not 4 or 8, -3 when a pointer is
+ * not aligned to its element (the workspace: 16 bytes); nothing is launched then.                                            */
+#define GWD_REGION_MAX 32
+#define GWD_REGION_RECORD 12
+#define GWD_REGION_CANDIDATES 8192
+int gwd_glass_regions(const uint8_t *labels, const uint16_t *depth_mm, const int32_t *sizes, int32_t B, int32_t Fh, int32_t Fw,
+                      int32_t max_regions, int32_t min_area, int32_t connectivity, int32_t max_candidates, int32_t lo_mm,
+                      int32_t hi_mm, void *workspace, uint8_t *region_map, int32_t *region_count, int32_t *region_total,
+                      int64_t *records, void *stream);
+int gwd_region_planes(const uint8_t *region_map, const uint16_t *depth_mm, const int32_t *sizes, const int32_t *region_count,
+                      const int64_t *records, int32_t B, int32_t Fh, int32_t Fw, int32_t max_regions, int32_t lo_mm,
+                      int32_t hi_mm, void *workspace, double *planes, void *stream);
+int gwd_depth_planar(const uint8_t *region_map, const uint16_t *depth_mm, const float *depth, const int32_t *sizes,
+                     const int32_t *region_count, const double *planes, int32_t B, int32_t Fh, int32_t Fw, int32_t max_regions,
+                     float min_depth, float max_depth, float *depth_planar, uint16_t *depth_planar_mm, void *stream);
 
 #ifdef __cplusplus
 }
