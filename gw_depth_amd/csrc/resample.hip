@@ -520,6 +520,9 @@ inline int flat_grid(int64_t total) {
     return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
 }
 
+// the vector kernels dereference uint4 / uint2 at base + k * pitch: a pitched operand (a channel slice of a wider map) must start on a vector
+inline bool misaligned(const void *p, int bytes) { return ((uintptr_t)p % (uintptr_t)bytes) != 0; }
+
 }  // namespace
 
 #define RS_DISPATCH(KERNEL, total, ...)                                                                     \
@@ -535,6 +538,7 @@ extern "C" int gwd_resample_forward(const void *x, void *y, int32_t B, int32_t H
     if (ldy == 0) ldy = C;
     if (ldy < C) return -1;
     if (ldy != C && (C % 4 || ldy % 4 || (dtype == GWD_BF16 && C % 8 == 0 && ldy % 8))) return -4;     // pitched output: vector kernels only
+    if (C % 4 == 0 && misaligned(y, dtype == GWD_BF16 && C % 8 ? 8 : 16)) return -4;                    // a slice that starts inside a vector
     const int64_t total = (int64_t)B * Ho * Wo * C;
     if (dtype == GWD_BF16 && C % 4 == 0) {
         if (C % 8 == 0) resample_fwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, Hs, Ws, Ho, Wo, C, mode, ldy);
@@ -621,6 +625,7 @@ extern "C" int gwd_resample_backward_sep(const void *gy, float *tmp, void *gx, i
     if (ldg == 0) ldg = C;
     if (ldg < C) return -1;
     if (C % 4 || ldg % 4 || (dtype == GWD_BF16 && C % 8 == 0 && ldg % 8)) return -4;       // caller uses gwd_resample_backward
+    if (misaligned(gy, dtype == GWD_BF16 && C % 8 ? 8 : 16)) return -4;                    // (on a contiguous copy of the slice)
     hipStream_t st = (hipStream_t)stream;
     const int vec = (dtype == GWD_BF16 && C % 8 == 0) ? 8 : 4;
     const int64_t t1 = (int64_t)B * Ho * Ws * (C / vec), t2 = (int64_t)B * Hs * Ws * (C / 4);
@@ -659,7 +664,7 @@ extern "C" int gwd_psp_pool_backward(const void *gpass, const void *g16, const v
     const int vec = dtype == GWD_BF16 ? 8 : (dtype == GWD_F32 ? 4 : 0);
     if (!vec) return -2;
     if (ldg == 0) ldg = C;
-    if (C % vec || ldg % vec || ldg < C) return -4;
+    if (C % vec || ldg % vec || ldg < C || misaligned(gpass, 16)) return -4;
     const int64_t total = (int64_t)B * H * W * (C / vec);
     if (dtype == GWD_BF16)
         psp_pool_bwd_kernel<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gpass, (const __bf16 *)g16, (const __bf16 *)g8, (const __bf16 *)g4, (const __bf16 *)g2, (__bf16 *)gx, B, H, W, C, ldg);

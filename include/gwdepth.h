@@ -460,7 +460,8 @@ int gwd_window_map_multi(const void *const *src, void *const *dst, const void *c
  * gathers over each source pixel's footprint (no atomics, bitwise reproducible).                    */
 enum { GWD_RESAMPLE_BILINEAR_AC = 0, GWD_RESAMPLE_NEAREST = 1 };
 /* ldy: pixel pitch of y in elements (0 = C).  ldy > C writes the result into a channel slice of a wider map (the PSP concat of
- * points_sample.py:114-122 without a concat pass); vector-sized C and ldy only, else -4.                          */
+ * points_sample.py:114-122 without a concat pass); vector-sized C and ldy only, else -4.  y itself must start on a vector of the
+ * kernel that runs (16 bytes; 8 for bf16 with C % 8 == 4), else -4: a slice that begins inside one cannot be written in place. */
 int gwd_resample_forward(const void *x, void *y, int32_t B, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo,
                          int32_t C, int32_t mode, int32_t ldy, int32_t dtype, void *stream);
 /* gate (may be NULL) [B][Hs][Ws][C] + gate_act (GWD_ACT_RELU / GWD_ACT_ELU): gx is multiplied by act'(.) of the activation whose
@@ -470,7 +471,8 @@ int gwd_resample_backward(const void *gy, void *gx, int32_t B, int32_t Hs, int32
 /* gwd_resample_backward as two separable passes (x, then y) through a caller-provided fp32 scratch tmp[B][Ho][Ws][C]:
  * the same sums in the same order, but 2r+2 taps per thread instead of (2r+2)^2 (13x faster at the 16x pyramid
  * branches).  Returns -4 when C is not a multiple of 16 bytes (use gwd_resample_backward).                       */
-/* ldg: pixel pitch of gy in elements (0 = C): the gradient of a channel slice read in place.                        */
+/* ldg: pixel pitch of gy in elements (0 = C): the gradient of a channel slice read in place; gy not aligned to the vector
+ * width (16 bytes; 8 for bf16 with C % 8 == 4) returns -4 as well.                                                 */
 int gwd_resample_backward_sep(const void *gy, float *tmp, void *gx, int32_t B, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo,
                               int32_t C, int32_t mode, int32_t ldg, int32_t dtype, void *stream);
 
@@ -484,7 +486,8 @@ int gwd_stride_place(const void *src, const void *residual, void *dst, int32_t B
 /* The four average pools of the PSP module (F.avg_pool2d with k = 16, 8, 4, 2; src/models/points/points_sample.py:107-113) from
  * ONE pass over x (B,H,W,C): p_k (B,H/k,W/k,C).  Backward in one pass as well: gx = g_pass + sum_k g_k[y/k][x/k] / k^2, where g_pass
  * (may be NULL; pixel pitch ldg, 0 = C) is the gradient that reaches the map directly - on this path the first channel slice of the
- * concat's gradient, read in place.  Any g_k may be NULL.  H, W >= 16; C (and ldg) multiples of 16 bytes, else -4.            */
+ * concat's gradient, read in place.  Any g_k may be NULL.  H, W >= 16; C (and ldg) multiples of 16 bytes and g_pass 16-byte
+ * aligned, else -4.                                                                                                    */
 int gwd_psp_pool_forward(const void *x, void *p16, void *p8, void *p4, void *p2, int32_t B, int32_t H, int32_t W, int32_t C,
                          int32_t dtype, void *stream);
 int gwd_psp_pool_backward(const void *g_pass, const void *g16, const void *g8, const void *g4, const void *g2, void *gx, int32_t B,
