@@ -1474,33 +1474,9 @@ def avg_pool(x, k):
     return _AvgPoolFn.apply(x, int(k))
 
 
-class _WinAttnPackedFn(torch.autograd.Function):
-    """qkv (W, 49, 3, heads, hd) packed as the qkv Linear writes it -> (W, 49, heads*hd).  `table` is the relative-position
-    bias PARAMETER (n_rel, heads), gathered through rel (49*49 int32) inside the kernels; its gradient is accumulated by the
-    backward kernel straight into the flat gradient buffer when the parameter is managed by engine.TrainStep (sink)."""
-
-    @staticmethod
-    def forward(ctx, qkv, table, rel, region, wpi, scale, sink):
-        qkv = qkv.contiguous()
-        W, N, _, H, D = qkv.shape
-        out = torch.empty((W, N, H, D), dtype=qkv.dtype, device=qkv.device)
-        tb = table.detach()
-        _lib().winattn_forward(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], out, tb, region, wpi, scale, rel_index=rel)
-        ctx.save_for_backward(qkv, tb, rel, region)
-        ctx.cfg = (wpi, scale)
-        ctx.sink = sink
-        return out.view(W, N, H * D)
-
-    @staticmethod
-    def backward(ctx, go):
-        qkv, tb, rel, region = ctx.saved_tensors
-        wpi, scale = ctx.cfg
-        W, N, _, H, D = qkv.shape
-        go = go.contiguous().view(W, N, H, D)
-        g = torch.empty_like(qkv)
-        gtab = _winattn_table_grad(tb, ctx.sink, lambda dtab, hm: _lib().winattn_backward(
-            qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], go, g[:, :, 0], g[:, :, 1], g[:, :, 2], tb, dtab, region, wpi, scale, rel_index=rel, head_major=hm), rel)
-        return g, gtab, None, None, None, None, None
+def _unit_last(t):
+    """The attention kernels take any window / token / head strides, but a unit channel stride."""
+    return t if t.stride(-1) == 1 else t.contiguous()
 
 
 def _winattn_table_grad(tb, sink, run, rel):
@@ -1525,93 +1501,77 @@ def _winattn_table_grad(tb, sink, run, rel):
     return None
 
 
+class QkvHandle:
+    """The packed qkv projection as ref_scores(..., handle=True) hands it on: a second output of that node, so the gradient of what
+    reads it travels to ref_scores' backward on an autograd edge.  That backward writes (or zeroes) the q slot of the arriving gradient
+    and never reads it: a consumer of the handle reads the k / v slots only and leaves the q slot of its gradient unwritten."""
+    __slots__ = ("qkv",)
+
+    def __init__(self, qkv):
+        self.qkv = qkv
+
+
 class _WinAttnFn(torch.autograd.Function):
-    """Separate q (W,49,H,D), k, v operands (any window/token/head strides, unit channel stride); bias table as above."""
+    """Window attention (W, 49, H*D).  Operand i of q / k / v is the given tensor (W, 49, H, D), or slot i of the packed projection
+    qkv (W, 49, 3, H, D) - as the qkv Linear writes it - where the tensor is None.  The operands taken from qkv get their gradient as
+    views of ONE packed tensor; a slot no operand came from is zero-filled when `fill`, else left unwritten (QkvHandle).  `table` is the
+    relative-position bias PARAMETER (n_rel, heads), gathered through rel (49*49 int32) inside the kernels; its gradient is accumulated
+    by the backward kernel straight into the flat gradient buffer when the parameter is managed by engine.TrainStep (sink)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, table, rel, region, wpi, scale, sink):
+    def forward(ctx, q, k, v, qkv, table, rel, region, wpi, scale, sink, fill):
+        own = [None if t is None else _unit_last(t) for t in (q, k, v)]
+        if qkv is not None:
+            qkv = qkv.contiguous()
+        q, k, v = (qkv[:, :, i] if t is None else t for i, t in enumerate(own))
         W, N, H, D = q.shape
         out = torch.empty((W, N, H, D), dtype=q.dtype, device=q.device)
         tb = table.detach()
-        fix = lambda t: t if t.stride(3) == 1 else t.contiguous()
-        q, k, v = fix(q), fix(k), fix(v)
         _lib().winattn_forward(q, k, v, out, tb, region, wpi, scale, rel_index=rel)
-        ctx.save_for_backward(q, k, v, tb, rel, region)
-        ctx.cfg = (wpi, scale)
+        ctx.save_for_backward(qkv, *own, tb, rel, region)
+        ctx.cfg = (wpi, scale, fill)
         ctx.sink = sink
         return out.view(W, N, H * D)
 
     @staticmethod
     def backward(ctx, go):
-        q, k, v, tb, rel, region = ctx.saved_tensors
-        wpi, scale = ctx.cfg
+        qkv, *own, tb, rel, region = ctx.saved_tensors
+        wpi, scale, fill = ctx.cfg
+        q, k, v = (qkv[:, :, i] if t is None else t for i, t in enumerate(own))
         W, N, H, D = q.shape
         go = go.contiguous().view(W, N, H, D)
-        gq, gk, gv = (torch.empty((W, N, H, D), dtype=q.dtype, device=q.device) for _ in range(3))
+        g = None if qkv is None else torch.empty_like(qkv)
+        gs = [g[:, :, i] if t is None else torch.empty((W, N, H, D), dtype=q.dtype, device=q.device) for i, t in enumerate(own)]
+        if g is not None and fill:
+            for i, t in enumerate(own):
+                if t is not None:
+                    g[:, :, i].zero_()
         gtab = _winattn_table_grad(tb, ctx.sink, lambda dtab, hm: _lib().winattn_backward(
-            q, k, v, go, gq, gk, gv, tb, dtab, region, wpi, scale, rel_index=rel, head_major=hm), rel)
-        return gq, gk, gv, gtab, None, None, None, None, None
+            q, k, v, go, *gs, tb, dtab, region, wpi, scale, rel_index=rel, head_major=hm), rel)
+        return (*(None if t is None else gt for t, gt in zip(own, gs)), g, gtab) + (None,) * 6
 
 
-class GradLink:
-    """Hands the packed qkv gradient of window_attention_qkv (k / v slots written) to ref_scores' backward, which writes the q slot and
-    returns the ONE tensor: q feeds ref_scores -> ... -> q_new -> window_attention_qkv, so that backward always runs first.  Without the
-    link each node returns a packed tensor with the other's slots zero-filled and autograd adds the two (2 fills + 1 add per block)."""
-    __slots__ = ("g",)
-
-    def __init__(self):
-        self.g = None
+def _win_attn(q, k, v, qkv, table, rel, region, windows_per_image, scale, fill=True):
+    return _WinAttnFn.apply(q, k, v, qkv, table, rel, region, int(windows_per_image), float(scale), _sink(table), fill)
 
 
-class _WinAttnQFn(torch.autograd.Function):
-    """Rewritten query q_new (W,49,H,D) against the k / v slots of the packed projection qkv (W,49,3,H,D): the gradient of qkv
-    comes back as ONE packed tensor (q slot zero) instead of two zero-filled select-backward temporaries and their sum."""
-
-    @staticmethod
-    def forward(ctx, q_new, qkv, table, rel, region, wpi, scale, sink, link=None):
-        ctx.link = link
-        q_new, qkv = q_new.contiguous(), qkv.contiguous()
-        W, N, H, D = q_new.shape
-        out = torch.empty((W, N, H, D), dtype=q_new.dtype, device=q_new.device)
-        tb = table.detach()
-        _lib().winattn_forward(q_new, qkv[:, :, 1], qkv[:, :, 2], out, tb, region, wpi, scale, rel_index=rel)
-        ctx.save_for_backward(q_new, qkv, tb, rel, region)
-        ctx.cfg = (wpi, scale)
-        ctx.sink = sink
-        return out.view(W, N, H * D)
-
-    @staticmethod
-    def backward(ctx, go):
-        q_new, qkv, tb, rel, region = ctx.saved_tensors
-        wpi, scale = ctx.cfg
-        W, N, H, D = q_new.shape
-        go = go.contiguous().view(W, N, H, D)
-        gq = torch.empty_like(q_new)
-        g = torch.empty_like(qkv)
-        if ctx.link is None:
-            g[:, :, 0].zero_()
-        gtab = _winattn_table_grad(tb, ctx.sink, lambda dtab, hm: _lib().winattn_backward(
-            q_new, qkv[:, :, 1], qkv[:, :, 2], go, gq, g[:, :, 1], g[:, :, 2], tb, dtab, region, wpi, scale, rel_index=rel, head_major=hm), rel)
-        if ctx.link is not None:                       # ref_scores' backward completes and returns it
-            ctx.link.g, g = g, None
-        return gq, g, gtab, None, None, None, None, None, None
-
-
-def window_attention_qkv(q_new, qkv, table, rel, region, windows_per_image, scale, link=None):
-    """softmax(scale*q_new k^T + bias (+shift mask)) v with k, v = qkv[:, :, 1], qkv[:, :, 2] (the 1/32 stage).  link: the GradLink also given
-    to the ref_scores call q_new descends from."""
-    return _WinAttnQFn.apply(q_new, qkv, table, rel, region, int(windows_per_image), float(scale), _sink(table), link)
+def window_attention_qkv(q_new, qkv, table, rel, region, windows_per_image, scale):
+    """softmax(scale*q_new k^T + bias (+shift mask)) v with k, v = qkv[:, :, 1], qkv[:, :, 2] (the 1/32 stage): the gradient of qkv
+    comes back as ONE packed tensor instead of two zero-filled select-backward temporaries and their sum.  qkv: the packed projection
+    (the q slot of its gradient is zero-filled), or the QkvHandle that ref_scores returned for it (the q slot is left to that backward)."""
+    handle = isinstance(qkv, QkvHandle)
+    return _win_attn(q_new, None, None, qkv.qkv if handle else qkv, table, rel, region, windows_per_image, scale, fill=not handle)
 
 
 def window_attention_packed(qkv, table, rel, region, windows_per_image, scale):
     """softmax(scale*q k^T + bias (+shift mask)) v over 49-token windows; qkv (W,49,3,H,D); bias(h,i,j) = table[rel[i*49+j], h]."""
-    return _WinAttnPackedFn.apply(qkv, table, rel, region, int(windows_per_image), float(scale), _sink(table))
+    return _win_attn(None, None, None, qkv, table, rel, region, windows_per_image, scale)
 
 
 def window_attention(q, k, v, table, rel, region, windows_per_image, scale):
     """Separate q / k / v operands (W, 49, H, D): bf16 on the matrix cores (csrc/mfattn.hip, head_dim 4..32), fp32 on the
     lane-per-row kernels (csrc/winattn.hip)."""
-    return _WinAttnFn.apply(q, k, v, table, rel, region, int(windows_per_image), float(scale), _sink(table))
+    return _win_attn(q, k, v, None, table, rel, region, windows_per_image, scale)
 
 
 class _RowAffineFn(torch.autograd.Function):
@@ -1654,11 +1614,14 @@ def row_affine(x, mu, logsigma):
 
 class _RefScoresFn(torch.autograd.Function):
     """ra (B, nwin*49, R, H) = scale * q . ref_k per head (multiscale_transformerr.py:296-298); q is read in place from the packed
-    qkv projection (W, 49, 3, H, hd) and its gradient comes back as ONE packed tensor (k and v slots zero)."""
+    qkv projection (W, 49, 3, H, hd) and its gradient comes back as ONE packed tensor.  With `handle` the node returns qkv itself next
+    to ra (an alias: no copy, no launch) for the other consumer of the projection, and the gradient of that output is the packed
+    tensor this backward completes: its k / v slots are kept, its q slot is never read - only overwritten with ra's gradient, or zeroed
+    where ra got none.  Without an arriving packed gradient the k / v slots are zero."""
 
     @staticmethod
-    def forward(ctx, qkv, ref_k, B, scale, link=None):
-        ctx.link = link
+    def forward(ctx, qkv, ref_k, B, scale, handle):
+        ctx.set_materialize_grads(False)
         qkv, ref_k = qkv.contiguous(), ref_k.contiguous()
         W, N, _, H, hd = qkv.shape
         R = ref_k.shape[1]
@@ -1666,17 +1629,17 @@ class _RefScoresFn(torch.autograd.Function):
         _lib().ref_scores_forward(qkv[:, :, 0], ref_k, ra, B, W // B, scale)
         ctx.save_for_backward(qkv, ref_k)
         ctx.cfg = (B, scale)
-        return ra
+        return (ra, qkv) if handle else ra
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, gqkv=None):
         qkv, ref_k = ctx.saved_tensors
         B, scale = ctx.cfg
-        gqkv = None
-        if ctx.link is not None:
-            gqkv, ctx.link.g = ctx.link.g, None         # k / v slots already hold window_attention_qkv's gradient
         if gqkv is None:
             gqkv = torch.zeros_like(qkv)
+        if g is None:
+            gqkv[:, :, 0].zero_()
+            return gqkv, None, None, None, None
         dk = torch.empty(ref_k.shape, dtype=torch.float32, device=g.device)
         _lib().ref_scores_backward(qkv[:, :, 0], ref_k, g.contiguous(), gqkv[:, :, 0], dk, B, qkv.shape[0] // B, scale)
         return gqkv, dk.to(ref_k.dtype), None, None, None
@@ -1705,9 +1668,13 @@ class _RefMixFn(torch.autograd.Function):
         return d_ra, dv.to(ref_v.dtype), None
 
 
-def ref_scores(qkv, ref_k, images, scale, link=None):
-    """qkv (images*nwin, 49, 3, H, hd) packed projection, ref_k (images, R, H*hd) -> (images, nwin*49, R, H)."""
-    return _RefScoresFn.apply(qkv, ref_k, int(images), float(scale), link)
+def ref_scores(qkv, ref_k, images, scale, handle=False):
+    """qkv (images*nwin, 49, 3, H, hd) packed projection, ref_k (images, R, H*hd) -> (images, nwin*49, R, H); handle: -> (that, the
+    QkvHandle to give window_attention_qkv in place of qkv, so that ONE packed gradient comes back for the projection)."""
+    if not handle:
+        return _RefScoresFn.apply(qkv, ref_k, int(images), float(scale), False)
+    ra, alias = _RefScoresFn.apply(qkv, ref_k, int(images), float(scale), True)
+    return ra, QkvHandle(alias)
 
 
 def ref_mix(ra, ref_v, heads):
@@ -1716,184 +1683,102 @@ def ref_mix(ra, ref_v, heads):
 
 
 class _TokAttnFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, scale):
-        fix = lambda t: t if t.stride(3) == 1 else t.contiguous()
-        q, k, v = fix(q), fix(k), fix(v)
-        W, N, H, R = q.shape
-        out = torch.empty((W, N, H, R), dtype=q.dtype, device=q.device)
-        _lib().tokattn_forward(q, k, v, out, scale)
-        ctx.save_for_backward(q, k, v)
-        ctx.scale = scale
-        return out.view(W, N, H * R)
+    """Class-token attention of one query, or of two that share k / v (token_attention_pair sends two only where the pair kernels
+    exist): the pair is one launch each way, and its gk / gv are already the sum autograd would form from two nodes.  Where the library
+    declines the pair call the single kernel runs per query and gk / gv are summed here.  ts: the queries, then k, v."""
 
     @staticmethod
-    def backward(ctx, go):
-        q, k, v = ctx.saved_tensors
-        W, N, H, R = q.shape
-        go = go.contiguous().view(W, N, H, R)
-        gq = torch.empty((W, N, H, R), dtype=q.dtype, device=q.device)
+    def forward(ctx, scale, *ts):
+        *qs, k, v = [_unit_last(t) for t in ts]
+        W, N, H, R = qs[0].shape
+        outs = [torch.empty((W, N, H, R), dtype=q.dtype, device=q.device) for q in qs]
+        if len(qs) == 1 or _lib().tokattn_pair_forward(*qs, k, v, *outs, scale) is False:
+            for q, o in zip(qs, outs):
+                _lib().tokattn_forward(q, k, v, o, scale)
+        ctx.save_for_backward(*qs, k, v)
+        ctx.scale = scale
+        return tuple(o.view(W, N, H * R) for o in outs)
+
+    @staticmethod
+    def backward(ctx, *gos):
+        *qs, k, v = ctx.saved_tensors
+        W, N, H, R = qs[0].shape
+        gos = [go.contiguous().view(W, N, H, R) for go in gos]
+        gqs = [torch.empty_like(go) for go in gos]
         gk = torch.empty(k.shape, dtype=k.dtype, device=k.device)
         gv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
-        _lib().tokattn_backward(q, k, v, go, gq, gk, gv, ctx.scale)
-        return gq, gk, gv, None
+        if len(qs) == 1 or _lib().tokattn_pair_backward(*qs, k, v, *gos, *gqs, gk, gv, ctx.scale) is False:
+            _lib().tokattn_backward(qs[0], k, v, gos[0], gqs[0], gk, gv, ctx.scale)
+            if len(qs) == 2:                             # summed as autograd sums two nodes
+                gk2, gv2 = torch.empty_like(gk), torch.empty_like(gv)
+                _lib().tokattn_backward(qs[1], k, v, gos[1], gqs[1], gk2, gv2, ctx.scale)
+                gk, gv = gk + gk2, gv + gv2
+        return (None, *gqs, gk, gv)
 
 
 def token_attention(q, k, v, scale):
     """Class-token attention: q (W,49,H,4), k/v (W,49,H,e) -> (W,49,4H); softmax over the e feature channels."""
-    return _TokAttnFn.apply(q, k, v, float(scale))
-
-
-class _TokAttnPairFn(torch.autograd.Function):
-    """token_attention for both class tokens at once (bf16): the pair shares k / v, one launch each way, and the backward's gk / gv are
-    already the sum autograd would have formed from two nodes."""
-
-    @staticmethod
-    def forward(ctx, q, q2, k, v, scale):
-        fix = lambda t: t if t.stride(3) == 1 else t.contiguous()
-        q, q2, k, v = fix(q), fix(q2), fix(k), fix(v)
-        W, N, H, R = q.shape
-        o = torch.empty((W, N, H, R), dtype=q.dtype, device=q.device)
-        o2 = torch.empty_like(o)
-        if _lib().tokattn_pair_forward(q, q2, k, v, o, o2, scale) is False:     # declined (alignment): the two single calls
-            _lib().tokattn_forward(q, k, v, o, scale)
-            _lib().tokattn_forward(q2, k, v, o2, scale)
-        ctx.save_for_backward(q, q2, k, v)
-        ctx.scale = scale
-        return o.view(W, N, H * R), o2.view(W, N, H * R)
-
-    @staticmethod
-    def backward(ctx, go, go2):
-        q, q2, k, v = ctx.saved_tensors
-        W, N, H, R = q.shape
-        go, go2 = go.contiguous().view(W, N, H, R), go2.contiguous().view(W, N, H, R)
-        gq, gq2 = torch.empty_like(go), torch.empty_like(go)
-        gk = torch.empty(k.shape, dtype=k.dtype, device=k.device)
-        gv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
-        if _lib().tokattn_pair_backward(q, q2, k, v, go, go2, gq, gq2, gk, gv, ctx.scale) is False:
-            gk2, gv2 = torch.empty_like(gk), torch.empty_like(gv)            # declined: two single calls, summed as autograd sums two nodes
-            _lib().tokattn_backward(q, k, v, go, gq, gk, gv, ctx.scale)
-            _lib().tokattn_backward(q2, k, v, go2, gq2, gk2, gv2, ctx.scale)
-            gk, gv = gk + gk2, gv + gv2
-        return gq, gq2, gk, gv, None
+    return _TokAttnFn.apply(float(scale), q, k, v)[0]
 
 
 def token_attention_pair(q, q2, k, v, scale):
     """token_attention(q, k, v), token_attention(q2, k, v); bf16 with e in {12, 16, 24}: one launch for the pair."""
     if q.dtype == torch.bfloat16 and k.shape[3] in (12, 16, 24):
-        return _TokAttnPairFn.apply(q, q2, k, v, float(scale))
+        return _TokAttnFn.apply(float(scale), q, q2, k, v)
     return token_attention(q, k, v, scale), token_attention(q2, k, v, scale)
 
 
-class _WindowGatherFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, shift):
-        x = x.contiguous()
-        B, H, W, C = x.shape
-        Hp, Wp = (H + 6) // 7 * 7, (W + 6) // 7 * 7
-        out = torch.empty((B * (Hp // 7) * (Wp // 7), 49, C), dtype=x.dtype, device=x.device)
-        _lib().window_map(x, out, B, H, W, C, shift, True)
-        ctx.cfg = (B, H, W, C, shift)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        B, H, W, C, shift = ctx.cfg
-        gx = torch.empty((B, H, W, C), dtype=g.dtype, device=g.device)
-        _lib().window_map(g.contiguous(), gx, B, H, W, C, shift, False)
-        return gx, None
-
-
-class _WindowScatterFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, win, B, H, W, shift, residual):
-        win = win.contiguous()
-        C = win.shape[-1]
-        out = torch.empty((B, H, W, C), dtype=win.dtype, device=win.device)
-        res = None if residual is None else residual.contiguous()
-        _lib().window_map(win, out, B, H, W, C, shift, False, residual=res)
-        ctx.cfg = (B, H, W, C, shift, tuple(win.shape), residual is not None and tuple(residual.shape))
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        B, H, W, C, shift, shape, rshape = ctx.cfg
-        g = g.contiguous()
-        gw = torch.empty(shape, dtype=g.dtype, device=g.device)
-        _lib().window_map(g, gw, B, H, W, C, shift, True)
-        return gw, None, None, None, None, (g.view(rshape) if rshape else None)
-
-
 def _window_map_each(srcs, dsts, B, H, W, Cs, shift, gather, residuals=None):
-    """window_map_multi, or - when the library declines the joint launch - window_map per map."""
-    if _lib().window_map_multi(srcs, dsts, B, H, W, Cs, shift, gather, residuals=residuals) is not False:
+    """One map: window_map.  Several: window_map_multi, or - when the library declines the joint launch - window_map per map."""
+    if len(srcs) > 1 and _lib().window_map_multi(srcs, dsts, B, H, W, Cs, shift, gather, residuals=residuals) is not False:
         return
     for i, (s, d, c) in enumerate(zip(srcs, dsts, Cs)):
         _lib().window_map(s, d, B, H, W, c, shift, gather, residual=None if residuals is None else residuals[i])
 
 
-class _WindowGatherMultiFn(torch.autograd.Function):
-    """window_gather of several maps of one geometry (features + class tokens of a Swin block) as ONE launch each way."""
+class _WindowMapFn(torch.autograd.Function):
+    """The 7x7 window partition (gather) or its reverse (scatter, with optional residual streams) of n maps of one geometry, as ONE
+    launch each way; args: n maps, then the residuals (n for a scatter, none for a gather).  The backward is the opposite map."""
 
     @staticmethod
-    def forward(ctx, shift, *xs):
-        xs = [x.contiguous() for x in xs]
-        B, H, W = xs[0].shape[:3]
-        Hp, Wp = (H + 6) // 7 * 7, (W + 6) // 7 * 7
-        outs = [torch.empty((B * (Hp // 7) * (Wp // 7), 49, x.shape[-1]), dtype=x.dtype, device=x.device) for x in xs]
-        _window_map_each(xs, outs, B, H, W, [x.shape[-1] for x in xs], shift, True)
-        ctx.cfg = (B, H, W, shift, [x.shape[-1] for x in xs])
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        B, H, W, shift, Cs = ctx.cfg
-        gs = [g.contiguous() for g in gs]
-        gxs = [torch.empty((B, H, W, c), dtype=g.dtype, device=g.device) for g, c in zip(gs, Cs)]
-        _window_map_each(gs, gxs, B, H, W, Cs, shift, False)
-        return (None,) + tuple(gxs)
-
-
-class _WindowScatterMultiFn(torch.autograd.Function):
-    """window_scatter (+ residual streams) of several maps of one geometry as ONE launch each way; args: n windows, then n residuals."""
-
-    @staticmethod
-    def forward(ctx, B, H, W, shift, n, *ts):
-        wins = [t.contiguous() for t in ts[:n]]
+    def forward(ctx, gather, B, H, W, shift, n, *ts):
+        srcs = [t.contiguous() for t in ts[:n]]
         ress = [None if r is None else r.contiguous() for r in ts[n:]]
-        Cs = [w.shape[-1] for w in wins]
-        outs = [torch.empty((B, H, W, c), dtype=w.dtype, device=w.device) for w, c in zip(wins, Cs)]
-        _window_map_each(wins, outs, B, H, W, Cs, shift, False, residuals=ress)
-        ctx.cfg = (B, H, W, shift, Cs, [tuple(w.shape) for w in wins], [r is not None and tuple(r.shape) for r in ts[n:]])
-        return tuple(outs)
+        Cs = [s.shape[-1] for s in srcs]
+        shape = (B * ((H + 6) // 7) * ((W + 6) // 7), 49) if gather else (B, H, W)
+        dsts = [torch.empty(shape + (c,), dtype=s.dtype, device=s.device) for s, c in zip(srcs, Cs)]
+        _window_map_each(srcs, dsts, B, H, W, Cs, shift, gather, residuals=ress or None)
+        ctx.cfg = (gather, B, H, W, shift, Cs, [tuple(s.shape) for s in srcs], [r is not None and tuple(r.shape) for r in ts[n:]])
+        return tuple(dsts)
 
     @staticmethod
     def backward(ctx, *gs):
-        B, H, W, shift, Cs, shapes, rshapes = ctx.cfg
+        gather, B, H, W, shift, Cs, shapes, rshapes = ctx.cfg
         gs = [g.contiguous() for g in gs]
-        gws = [torch.empty(sh, dtype=g.dtype, device=g.device) for g, sh in zip(gs, shapes)]
-        _window_map_each(gs, gws, B, H, W, Cs, shift, True)
-        return (None,) * 5 + tuple(gws) + tuple((g.view(rs) if rs else None) for g, rs in zip(gs, rshapes))
+        outs = [torch.empty(sh, dtype=g.dtype, device=g.device) for g, sh in zip(gs, shapes)]
+        _window_map_each(gs, outs, B, H, W, Cs, shift, not gather)
+        return (None,) * 6 + tuple(outs) + tuple((g.view(rs) if rs else None) for g, rs in zip(gs, rshapes))
 
 
 def window_gather_multi(xs, shift):
     """[window_gather(x, shift) for x in xs] (maps of one (B, H, W), any channel counts, at most 4) in one launch."""
-    return _WindowGatherMultiFn.apply(int(shift), *xs)
+    B, H, W = xs[0].shape[:3]
+    return _WindowMapFn.apply(True, B, H, W, int(shift), len(xs), *xs)
 
 
 def window_scatter_multi(wins, B, H, W, shift, residuals):
     """[window_scatter(w, B, H, W, shift, r) for w, r in zip(wins, residuals)] in one launch."""
-    return _WindowScatterMultiFn.apply(int(B), int(H), int(W), int(shift), len(wins), *wins, *residuals)
+    return _WindowMapFn.apply(False, int(B), int(H), int(W), int(shift), len(wins), *wins, *residuals)
 
 
 def window_gather(x, shift):
     """(B,H,W,C) -> (B*nWin, 49, C): zero-pad to multiples of 7, cyclic shift by -shift, 7x7 window partition."""
-    return _WindowGatherFn.apply(x, int(shift))
+    return window_gather_multi([x], shift)[0]
 
 
 def window_scatter(win, B, H, W, shift, residual=None):
     """Inverse of window_gather (window reverse, un-shift, crop) -> (B,H,W,C) [+ residual, any shape with B*H*W*C elements]."""
-    return _WindowScatterFn.apply(win, int(B), int(H), int(W), int(shift), residual)
+    return window_scatter_multi([win], B, H, W, shift, [residual])[0]
 
 
 class _InormGeluFn(torch.autograd.Function):

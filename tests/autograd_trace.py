@@ -1,4 +1,5 @@
-"""Trace witness of the conv-family autograd nodes (ops._ConvFn, _PadConvFn, _LayerNormFn, _ConvLnFn, _PyramidTailFn).
+"""Trace witness of the conv-family autograd nodes (ops._ConvFn, _PadConvFn, _LayerNormFn, _ConvLnFn, _PyramidTailFn) and of the
+Swin / class-token attention family (ops._WinAttnFn, _RefScoresFn, _RefMixFn, _TokAttnFn, _WindowMapFn).
 
 A Recorder stands in for the device library (hip.set_library) and writes one text line per library method call: the method name,
 the arguments without a default in order, every keyword whose value is not its default as `name=value`, scalars verbatim, every tensor
@@ -12,7 +13,8 @@ firings leaves every line as it is: tests/golden/autograd_trace.txt holds the li
 Two modes:
   dry (CPU suite)    nothing is computed, outputs stay as allocated; the methods that can decline (conv_forward with ln= or a GELU
                      gate, act_backward_colsum, layernorm_backward, stride_place, resample_backward with a gate,
-                     resample_backward_sep) answer from the case's script, so every fallback arm is forced without a special shape.
+                     resample_backward_sep, tokattn_pair_forward / _backward, window_map_multi) answer from the case's script, so
+                     every fallback arm is forced without a special shape.
   delegating (gpu)   the same lines, every call forwarded to the real library, whose answers decide the path.
 
 ATen operations that launch work are part of the trace in BOTH modes (`aten <operator> <shapes and scalars>`, through a
@@ -21,14 +23,14 @@ backward's device thread, and the gpu sections of the golden file show the backw
 library does inside a call (its zero page) is not logged.
 
 CASES is the one list both modes use (the gpu-only cases need real answers or the x.is_cuda arms); ARMS, below it, names the case
-that takes each arm of the five nodes."""
+that takes each arm of the nodes."""
 import contextlib
 import inspect
 
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
-from gw_depth_amd import hip, ops
+from gw_depth_amd import hip, model, ops
 from gw_depth_amd.hip import ACT_ELU, ACT_GELU, ACT_NONE, ACT_RELU
 
 # the keyword defaults of a convolution descriptor: conv_forward / conv_wgrad take them as **kw
@@ -110,7 +112,8 @@ class Recorder:
             if kw.get("ln") is not None or (kw.get("gate") is not None and kw.get("gate_act") == ACT_GELU):
                 return None if self._scripted(name) else False
             return None
-        if name in ("act_backward_colsum", "stride_place", "resample_backward_sep"):
+        if name in ("act_backward_colsum", "stride_place", "resample_backward_sep", "tokattn_pair_forward", "tokattn_pair_backward",
+                    "window_map_multi"):
             return self._scripted(name)
         if name == "layernorm_backward":
             return self._scripted(name) if (kw.get("gskip") is not None or kw.get("elu_input")) else True
@@ -193,24 +196,38 @@ class Builder:
         with self._muted():
             return (torch.randn(*shape, generator=self.gen) * 0.5).to(dtype or self.dtype).to(self.dev)
 
-    def x(self, *shape, grad=True):
-        t = self.randn(*shape).requires_grad_(grad)
+    def leaf(self, t, grad=True):
+        t.requires_grad_(grad)
         self.leaves["x%d" % sum(k.startswith("x") for k in self.leaves)] = t
         return t
+
+    def x(self, *shape, grad=True):
+        return self.leaf(self.randn(*shape), grad)
 
     def mult(self, *shape):
         with self._muted():
             return ((torch.rand(*shape, generator=self.gen) > 0.3).to(self.dtype) * 2).to(self.dev)
 
+    def _register(self, name, p, sink):
+        if sink:
+            p._gwd_grad = torch.zeros_like(p.data)
+            p._gwd_hook = lambda: self.rec.lines.append("hook %s" % name)
+        self.leaves[name] = p
+        return p
+
     def p(self, name, *shape, sink=True, ones=False):
         with self._muted():
             t = self.randn(*shape, dtype=torch.float32)
-            p = torch.nn.Parameter(t + 1.0 if ones else t)
-            if sink:
-                p._gwd_grad = torch.zeros_like(p.data)
-                p._gwd_hook = lambda: self.rec.lines.append("hook %s" % name)
-        self.leaves[name] = p
-        return p
+            return self._register(name, torch.nn.Parameter(t + 1.0 if ones else t), sink)
+
+    def module(self, make, sink=True):
+        """make() -> a module; its parameters become leaves under their named_parameters() names, with values from the case's generator."""
+        with self._muted():
+            m = make().to(self.dev)
+            for name, p in m.named_parameters():
+                p.data.copy_(self.randn(*p.shape, dtype=torch.float32))
+                self._register(name, p, sink)
+        return m
 
 
 class Case:
@@ -400,6 +417,90 @@ def _ln6_bf16(T):
     return ops.layer_norm(T.x(B, H, W, 6), T.p("gamma", 6, ones=True), T.p("beta", 6), fanout=True)
 
 
+# ---- the Swin / class-token attention family: 2 windows of 49 tokens, 16 heads of 4 channels (dim 64), token width e = 12, R = 7
+NW, NT, HD, TE, NREF = 2, 49, 4, 12, 7
+DIM = model.HEADS * HD
+RHD = 8                     # the ref_scores kernels of the device start at head dim 8: the cases that run them use dim 128
+RDIM = model.HEADS * RHD
+
+
+def _win_operands(T, sink, region):
+    """table parameter, rel index, region table, windows per image, scale"""
+    table = T.p("table", (2 * model.WS - 1) ** 2, model.HEADS, sink=sink)
+    with T._muted():
+        rel = model.relative_position_index().reshape(-1).to(torch.int32).to(T.dev)
+        reg = (torch.arange(NW * NT, dtype=torch.int32).view(NW, NT) % 3).to(T.dev) if region else None
+    return table, rel, reg, (NW if region else 1), HD ** -0.5
+
+
+def _win_packed(sink=True, region=False):
+    def body(T):
+        return ops.window_attention_packed(T.x(NW, NT, 3, model.HEADS, HD), *_win_operands(T, sink, region))
+    return body
+
+
+def _win_separate(sink=True, region=False, strided=False):
+    def body(T):
+        q = T.x(NW, NT, HD, model.HEADS).transpose(2, 3) if strided else T.x(NW, NT, model.HEADS, HD)      # strided: no unit channel stride
+        return ops.window_attention(q, T.x(NW, NT, model.HEADS, HD), T.x(NW, NT, model.HEADS, HD), *_win_operands(T, sink, region))
+    return body
+
+
+def _win_query(sink=True, region=False):
+    def body(T):
+        return ops.window_attention_qkv(T.x(NW, NT, model.HEADS, HD), T.x(NW, NT, 3, model.HEADS, HD), *_win_operands(T, sink, region))
+    return body
+
+
+def _win_block(sink=True, region=False):
+    """model.WindowAttention whole: ref_scores and window_attention_qkv share ONE packed qkv gradient."""
+    def body(T):
+        att = T.module(lambda: model.WindowAttention(RDIM), sink=sink)
+        with T._muted():
+            att.rel_index()
+            reg = (torch.arange(NW * NT, dtype=torch.int32).view(NW, NT) % 3).to(T.dev) if region else None
+        return att(T.x(NW, NT, RDIM), T.x(1, NREF, RDIM), reg)
+    return body
+
+
+def _ref_alone(T):
+    ra = ops.ref_scores(T.x(NW, NT, 3, model.HEADS, RHD), T.x(1, NREF, RDIM), 1, RHD ** -0.5)
+    return ops.ref_mix(ra, T.x(1, NREF, RDIM), model.HEADS)
+
+
+def _tok_single(T):
+    return ops.token_attention(T.x(NW, NT, model.HEADS, 4), T.x(NW, NT, model.HEADS, TE), T.x(NW, NT, model.HEADS, TE), 0.5)
+
+
+def _tok_pair(T):
+    return ops.token_attention_pair(T.x(NW, NT, model.HEADS, 4), T.x(NW, NT, model.HEADS, 4), T.x(NW, NT, model.HEADS, TE),
+                                    T.x(NW, NT, model.HEADS, TE), 0.5)
+
+
+def _tok_pair_misaligned(T):
+    # the operands of test_token_attention_pair_declined_falls_back[offset_4_bytes]: q starts 4 bytes past an 8-byte boundary
+    nwin, e = 5, 16
+    q = T.leaf(T.randn(nwin * NT * model.HEADS * 4 + 2)[2:].view(nwin, NT, model.HEADS, 4))
+    return ops.token_attention_pair(q, T.x(nwin, NT, model.HEADS, 4), T.x(nwin, NT, model.HEADS, e), T.x(nwin, NT, model.HEADS, e), 0.5)
+
+
+MB, MH, MW = 1, 8, 10        # padded to 14 x 14: 4 windows
+
+
+def _map_single(shift, res):
+    def body(T):
+        win = ops.window_gather(T.x(MB, MH, MW, DIM), shift)
+        return ops.window_scatter(win, MB, MH, MW, shift, residual=T.x(MB, MH * MW, DIM) if res else None)
+    return body
+
+
+def _map_multi(shift, Cs=(DIM, 64, 64), res=(True, True, True)):
+    def body(T):
+        wins = ops.window_gather_multi([T.x(MB, MH, MW, c) for c in Cs], shift)
+        return ops.window_scatter_multi(list(wins), MB, MH, MW, shift, [T.x(MB, MH * MW, c) if r else None for c, r in zip(Cs, res)])
+    return body
+
+
 BF16 = torch.bfloat16
 
 CASES = [
@@ -482,6 +583,42 @@ CASES = [
     Case("gpu_bias_not_in_wgrad_fp32", _bias_in_wgrad, gpu_only=True),
     Case("gpu_cout6_bf16_colsum_declines", _cout6_bf16, gpu_only=True, dtype=BF16),
     Case("gpu_ln6_bf16_skip_declines", _ln6_bf16, gpu_only=True, dtype=BF16),
+    # window attention
+    Case("win_packed_sink", _win_packed()),
+    Case("win_packed_nosink", _win_packed(sink=False)),
+    Case("win_packed_region", _win_packed(region=True)),
+    Case("win_packed_queued", _win_packed(), pooled=True),
+    Case("win_separate_sink", _win_separate()),
+    Case("win_separate_nosink_region", _win_separate(sink=False, region=True)),
+    Case("win_separate_strided_q", _win_separate(strided=True)),
+    Case("win_separate_queued", _win_separate(), pooled=True),
+    Case("win_query_sink", _win_query()),
+    Case("win_query_nosink", _win_query(sink=False)),
+    Case("win_query_region", _win_query(region=True)),
+    Case("win_query_queued", _win_query(), pooled=True),
+    Case("win_block_sink", _win_block()),
+    Case("win_block_nosink_region", _win_block(sink=False, region=True)),
+    Case("win_block_queued", _win_block(), pooled=True),
+    Case("ref_scores_mix_alone", _ref_alone),
+    Case("gpu_win_packed_bf16", _win_packed(), gpu_only=True, dtype=BF16),
+    Case("gpu_win_packed_bf16_nosink_queued", _win_packed(sink=False), pooled=True, gpu_only=True, dtype=BF16),
+    Case("gpu_win_query_bf16", _win_query(), gpu_only=True, dtype=BF16),
+    Case("gpu_win_query_bf16_nosink_queued", _win_query(sink=False), pooled=True, gpu_only=True, dtype=BF16),
+    Case("gpu_win_block_bf16_queued", _win_block(), pooled=True, gpu_only=True, dtype=BF16),
+    # token attention
+    Case("tok_single", _tok_single),
+    Case("tok_pair_taken", _tok_pair, dtype=BF16),
+    Case("tok_pair_forward_declined", _tok_pair, script={"tokattn_pair_forward": [False]}, dtype=BF16),
+    Case("tok_pair_backward_declined", _tok_pair, script={"tokattn_pair_backward": [False]}, dtype=BF16),
+    Case("tok_pair_fp32_two_singles", _tok_pair),
+    Case("gpu_tok_pair_misaligned_q_declines", _tok_pair_misaligned, gpu_only=True, dtype=BF16),
+    # window maps
+    Case("map_single", _map_single(0, False)),
+    Case("map_single_shift_residual", _map_single(3, True)),
+    Case("map_multi_taken", _map_multi(3)),
+    Case("map_multi_declined", _map_multi(0), script={"window_map_multi": [False, False, False, False]}),
+    Case("map_multi_one_residual_none", _map_multi(3, res=(True, False, True))),
+    Case("gpu_map_multi_fp32_width6_declines", _map_multi(3, Cs=(16, 6, 6), res=(True, False, True)), gpu_only=True),
 ]
 ARMS = """Which case takes which arm (dry mode unless the name starts with gpu_).
 
@@ -521,6 +658,21 @@ _ConvLnFn           fused / declined forward: conv_ln_fused / conv_ln_declined; 
                     conv_ln_inference / conv_ln_inference_declined
 _PyramidTailFn      nlow < branches (concat forward / backward, separable resample taken / declined): tail_nlow1_sink /
                     tail_nlow1_sep_declined;  nlow == branches, no sinks: tail_nlow2_nosink;  pooled scratch: tail_nlow*_queued
+_WinAttnFn          q / k / v all slots of qkv: win_packed_*;  all given: win_separate_*;  q given, k / v slots: win_query_*, win_block_*
+                    operand without a unit channel stride copied: win_separate_strided_q;  region table (2 windows per image): *_region
+                    free q slot of the packed gradient zero-filled: win_query_*;  left to ref_scores' backward: win_block_*
+  table gradient    sink / fresh zeros (dry: straight into either): *_sink / *_nosink;  head-major scratch, transposed add into the sink /
+                    transposed copy (tb.is_cuda): gpu_win_packed_bf16, gpu_win_query_bf16 / gpu_win_*_bf16_nosink_queued and the gpu
+                    sections of every win_* case;  pooled scratch offsets: *_queued
+_RefScoresFn        packed gradient arrives on the handle's edge, q slot written into it: win_block_* (gpu_win_block_bf16_queued);
+                    no handle, zeros_like: ref_scores_mix_alone;  ra without a gradient (q slot zeroed): tests/test_qkv_handle.py
+_RefMixFn           win_block_*, ref_scores_mix_alone
+_TokAttnFn          one query: tok_single, tok_pair_fp32_two_singles (two nodes, autograd adds gk / gv);  pair taken both ways:
+                    tok_pair_taken;  forward declined / backward declined (singles, gk / gv summed in the node): tok_pair_forward_declined
+                    / tok_pair_backward_declined;  real decline both ways (q 4 bytes past an 8-byte boundary): gpu_tok_pair_misaligned_q_declines
+_WindowMapFn        one map (window_map, window_map_multi never asked), without / with residual, shift 0 / 3: map_single /
+                    map_single_shift_residual;  several maps joint / declined four times (per map): map_multi_taken / map_multi_declined;
+                    a residual None: map_multi_one_residual_none;  real decline (fp32 rows of 6 channels): gpu_map_multi_fp32_width6_declines
 """
 
 

@@ -450,10 +450,12 @@ def test_upsample_taps_collapse_and_fold(dev, Cout, Cin):
         dev.upsample_taps_fold(D.cuda(), dw0.cuda().permute(0, 2, 1, 3))
 
 
-def test_packed_qkv_gradient_link_of_the_1_32_stage(dev, monkeypatch):
-    """ops.GradLink: window_attention_qkv's backward hands its packed gradient (k / v slots) to ref_scores' backward, which writes the q slot -
-    same gradients as the two zero-filled tensors autograd used to add."""
-    from gw_depth_amd import model as M, ops
+def test_packed_qkv_gradient_link_of_the_1_32_stage(dev):
+    """The qkv handle of ops.ref_scores: window_attention_qkv's backward hands its packed gradient (k / v slots) to ref_scores' backward on
+    an autograd edge, which writes the q slot - same gradients as the two zero-filled tensors autograd adds when the same pieces are
+    composed on the plain qkv (tests/test_qkv_handle.py: compose)."""
+    from gw_depth_amd import model as M
+    from tests.test_qkv_handle import compose
     torch.manual_seed(0)
     att = M.WindowAttention(512).cuda()
     for p in att.parameters():
@@ -463,13 +465,12 @@ def test_packed_qkv_gradient_link_of_the_1_32_stage(dev, monkeypatch):
     wgt = torch.randn(18, 49, 512, device="cuda")
     ps = [p for p in att.parameters() if p.requires_grad]
 
-    def run():
-        y = att(xw, x_ref, None)
+    def run(forward):
+        y = forward()
         return y, torch.autograd.grad((y.float() * wgt).sum(), [xw, x_ref] + ps, allow_unused=True)
 
-    y1, g_link = run()
-    monkeypatch.setattr(ops, "GradLink", lambda: None)
-    y2, g_two = run()
+    y1, g_link = run(lambda: att(xw, x_ref, None))
+    y2, g_two = run(lambda: compose(att, xw, x_ref, handle=False)[0])
     torch.cuda.synchronize()
     assert torch.equal(y1, y2)
     n = 0
