@@ -44,6 +44,7 @@ ENTRY_POINTS = [
     "gwd_segment_stats", "gwd_health_decide", "gwd_adamw_step_guarded",
     "gwd_adamw_step_ema", "gwd_ema_swap",
     "gwd_glass_regions", "gwd_region_planes", "gwd_depth_planar",
+    "gwd_line_profiles",
 ]
 
 
@@ -130,6 +131,9 @@ AUGMENT_BATCH = 16        # frames per grouped augmentation launch
 REGION_MAX = 32           # GWD_REGION_MAX: kept regions per image, at most
 REGION_RECORD = 12        # GWD_REGION_RECORD: int64 fields of a region's record
 REGION_CANDIDATES = 8192  # GWD_REGION_CANDIDATES: default length of the candidate list per image
+PROFILE_MAX_LINES = 2048      # GWD_PROFILE_MAX_LINES: rows per image of gwd_line_profiles
+PROFILE_MAX_SAMPLES = 2048    # GWD_PROFILE_MAX_SAMPLES: samples per line, at most
+PROFILE_COUNTS = 12           # GWD_PROFILE_COUNTS: int32 fields of a line's counts
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
 COLOR_ADJUST, COLOR_SUMS = 0, 1
 
@@ -317,6 +321,7 @@ class HipLibrary:
         L.gwd_glass_regions.argtypes = [vp] * 3 + [i32] * 9 + [vp] * 6
         L.gwd_region_planes.argtypes = [vp] * 5 + [i32] * 6 + [vp] * 3
         L.gwd_depth_planar.argtypes = [vp] * 6 + [i32] * 4 + [f32, f32] + [vp] * 3
+        L.gwd_line_profiles.argtypes = [vp, i32] + [vp] * 7 + [i32] * 4 + [ctypes.c_double] + [i32] * 5 + [vp] * 5
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1319,6 +1324,32 @@ class HipLibrary:
             _ptr(region_map), _ptr(depth_mm), _ptr(depth), _ptr(sizes), _ptr(region_count), _ptr(planes), B, Fh, Fw, R, float(dmin),
             float(dmax), _ptr(depth_planar), _ptr(depth_planar_mm),
             self._stream(region_map, depth_mm, depth, sizes, region_count, planes, depth_planar, depth_planar_mm)), "gwd_depth_planar")
+
+    def line_profiles(self, lines, count, order, labels, depth_mm, sizes, region_map, intrinsics, offset, max_samples, lo_mm, hi_mm,
+                      hi, lo, counts, fits, kind, line_points):
+        """gwd_line_profiles: lines (B,C,4) float32 or float64, count (B,) int32, order (B,C) int32 or None, labels uint8 / depth_mm
+        uint16 (B,Fh,Fw), sizes (B,2) int32, region_map uint8 (B,Fh,Fw) or None, intrinsics (B,4) float64 with line_points (B,C,2,3)
+        float64, or both None; outputs counts (B,C,12) int32, fits (B,C,3,5) float64, kind (B,C) int32."""
+        if lines.dtype not in (torch.float32, torch.float64):
+            raise TypeError("gwd_line_profiles: lines must be float32 or float64, got %s" % lines.dtype)
+        self._typed("gwd_line_profiles", ((count, torch.int32), (order, torch.int32), (labels, torch.uint8), (depth_mm, torch.uint16),
+                                          (sizes, torch.int32), (region_map, torch.uint8), (intrinsics, torch.float64),
+                                          (counts, torch.int32), (fits, torch.float64), (kind, torch.int32), (line_points, torch.float64)))
+        B, Fh, Fw = labels.shape
+        C = lines.shape[1] if lines.dim() == 3 else -1
+        shape = (B, Fh, Fw)
+        if tuple(lines.shape) != (B, C, 4) or count.numel() != B or (order is not None and tuple(order.shape) != (B, C)) \
+                or tuple(depth_mm.shape) != shape or tuple(sizes.shape) != (B, 2) or (region_map is not None and tuple(region_map.shape) != shape) \
+                or (intrinsics is None) != (line_points is None) or (intrinsics is not None and tuple(intrinsics.shape) != (B, 4)) \
+                or (line_points is not None and tuple(line_points.shape) != (B, C, 2, 3)) or tuple(counts.shape) != (B, C, PROFILE_COUNTS) \
+                or tuple(fits.shape) != (B, C, 3, 5) or tuple(kind.shape) != (B, C):
+            raise ValueError("gwd_line_profiles: operand sizes do not match (B, C, Fh, Fw) = (%d, %d, %d, %d)" % (B, C, Fh, Fw))
+        self._check(self.lib.gwd_line_profiles(
+            _ptr(lines), 1 if lines.dtype == torch.float64 else 0, _ptr(count), _ptr(order), _ptr(labels), _ptr(depth_mm), _ptr(sizes),
+            _ptr(region_map), _ptr(intrinsics), B, C, Fh, Fw, float(offset), int(max_samples), int(lo_mm), int(hi_mm), int(hi), int(lo),
+            _ptr(counts), _ptr(fits), _ptr(kind), _ptr(line_points),
+            self._stream(lines, count, order, labels, depth_mm, sizes, region_map, intrinsics, counts, fits, kind, line_points)),
+            "gwd_line_profiles")
 
 
 _LIB = None

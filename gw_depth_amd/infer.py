@@ -26,6 +26,8 @@ RESULT_KEYS = ("depth", "depth_mm", "labels", "scores", "lines", "order", "count
 NMS_KEYS = ("nms_lines", "nms_scores", "nms_ids", "nms_count")          # added to a result by a session built with line_nms=
 _REGION_OPTIONS = ("max_regions", "min_area", "connectivity", "min_depth", "max_depth", "planes", "planar", "max_candidates")
 REGION_KEYS = ops.REGION_KEYS                                          # added to predict_frames' result by a session built with regions=
+_PROFILE_OPTIONS = ("offset", "max_samples", "min_depth", "max_depth", "hi", "lo")
+PROFILE_KEYS = ops.PROFILE_KEYS                                        # ... with line_profiles= (line_points only when intrinsics are passed)
 
 
 def _count_memsets_in(fn):
@@ -84,11 +86,19 @@ class InferenceSession:
     and the depth those planes predict - computed from its own labels / depth_mm / depth / sizes behind the resized
     post-processing, on the session's stream, as fresh tensors, with no host sync.  predict() does not take part.
 
+    LINE PROFILES.  line_profiles=None (the default): nothing is allocated, predict_frames issues the launches and returns the keys
+    it always did.  line_profiles=True or a dict of ops.line_profiles' options (offset, max_samples, hi, lo; min_depth / max_depth
+    default to the session's): predict_frames also returns PROFILE_KEYS - every detected line walked through the frame's own labels /
+    depth_mm (and region_map, with regions=) in one launch behind them: the depth of its two ends, the side the glass lies on, the
+    pane it frames.  With line_nms the rows are the NMS survivors (nms_lines, nms_count; the mirrored twin's candidates included
+    under ensemble=True), without it the count[b] lines above score_thresh, reached through `order`.  predict_frames(intrinsics=)
+    adds line_points, the ends in camera coordinates.  predict() does not take part.
+
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
 
     def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6,
-                 line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None):
+                 line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None, line_profiles=None):
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
         if line_nms_order not in ("score", "query"):
@@ -108,6 +118,13 @@ class InferenceSession:
             raise TypeError("regions: unknown option(s) %s (known: %s)" % (sorted(set(regions) - set(_REGION_OPTIONS)), ", ".join(_REGION_OPTIONS)))
         self.regions = None if regions is None else ops.check_region_options(
             **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(regions if isinstance(regions, dict) else {})))
+        if line_profiles is not None and line_profiles is not True and not isinstance(line_profiles, dict):
+            raise TypeError("line_profiles must be None, True or a dict of ops.line_profiles' options, got %r" % (line_profiles,))
+        if isinstance(line_profiles, dict) and set(line_profiles) - set(_PROFILE_OPTIONS):
+            raise TypeError("line_profiles: unknown option(s) %s (known: %s)"
+                            % (sorted(set(line_profiles) - set(_PROFILE_OPTIONS)), ", ".join(_PROFILE_OPTIONS)))
+        self.line_profiles = None if line_profiles is None else ops.check_line_profile_options(
+            **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(line_profiles if isinstance(line_profiles, dict) else {})))
         self._graphs = OrderedDict()
         self._pool = None
         self._gstream = None
@@ -364,7 +381,7 @@ class InferenceSession:
             frame = frame.pin_memory()
         return frame.to(device, non_blocking=True)
 
-    def predict_frames(self, frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False):
+    def predict_frames(self, frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False, intrinsics=None):
         """Decoded camera frames in, results at each frame's own size out.  frames: list of uint8 (h,w,3) tensors, host or device,
         of any sizes: at most hip.AUGMENT_BATCH (16) per call, half that with ensemble=True (the forward batch is 2B); no side
         above 16384.  The reference's evaluation transform (RandomResize([size], max_size), ToTensor, Normalize:
@@ -379,6 +396,9 @@ class InferenceSession:
 
         A session with regions= adds REGION_KEYS (GLASS REGIONS above), at frame size.
 
+        A session with line_profiles= adds PROFILE_KEYS (LINE PROFILES above); intrinsics: (B,4) (fx, fy, cx, cy) per frame at frame
+        size (a tensor or nested sequence) adds line_points - a session without line_profiles raises.
+
         -> RESULT_KEYS + "net_sizes": depth / depth_mm / labels (B, Fh, Fw) with (Fh, Fw) the largest frame of the call (outside
         a frame 0 / 0 / 255), sizes (B,2) the FRAME sizes, net_sizes (B,2) the un-padded network sizes, scores / lines / order /
         count as predict() gives them for the B frames, lines in frame pixels.  The dense results, sizes and net_sizes are fresh
@@ -391,6 +411,13 @@ class InferenceSession:
             if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or 0 in f.shape:
                 raise ValueError("predict_frames: frames are uint8 (h, w, 3) tensors")
         dev = self._device()
+        if intrinsics is not None:
+            if self.line_profiles is None:
+                raise ValueError("predict_frames: intrinsics need a session built with line_profiles=")
+            intrinsics = torch.as_tensor(intrinsics, dtype=torch.float64)
+            if tuple(intrinsics.shape) != (B, 4):
+                raise ValueError("predict_frames: intrinsics must be (%d, 4) = (fx, fy, cx, cy) per frame, got %s" % (B, tuple(intrinsics.shape)))
+            intrinsics = intrinsics.to(dev, non_blocking=True)
         aug = data.DeviceAugment(train=False, test_size=size, max_size=max_size)
         frame_sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
         net_sizes = [data.resized_shape(w, h, size, max_size) for h, w in frame_sizes]
@@ -412,9 +439,18 @@ class InferenceSession:
                 raw["pred_depth"][-1], raw["pred_seg"], nsz, fsz, (max(s[0] for s in frame_sizes), max(s[1] for s in frame_sizes)),
                 self.min_depth, self.max_depth, twin=B if ensemble else 0)
             regions = None if self.regions is None else ops.glass_regions(labels, mm, fsz, depth=depth, **self.regions)
+            profiles = None
+            if self.line_profiles is not None:             # the rows: the NMS survivors, or the lines above score_thresh through `order`
+                nms = self.line_nms is not None
+                profiles = ops.line_profiles(post["nms_lines" if nms else "lines"][:B], post["nms_count" if nms else "count"][:B], labels,
+                                             mm, fsz, order=None if nms else post["order"][:B],
+                                             region_map=None if regions is None else regions["region_map"], intrinsics=intrinsics,
+                                             **self.line_profiles)
         res = {"depth": depth, "depth_mm": mm, "labels": labels, "sizes": fsz, "net_sizes": nsz}
         if regions is not None:
             res.update(regions)
+        if profiles is not None:
+            res.update(profiles)
         for k in ("scores", "lines", "order", "count") + (NMS_KEYS if self.line_nms is not None else ()):
             res[k] = post[k][:B].clone() if copy else post[k][:B]
         return res

@@ -2140,3 +2140,84 @@ def glass_regions(labels, depth_mm, sizes, max_regions=32, min_area=100, connect
         lib.depth_planar(res["region_map"], depth_mm, None if depth is None else depth.contiguous(), sizes, res["region_count"],
                          res["planes"], opt["min_depth"], opt["max_depth"], res["depth_planar"], res["depth_planar_mm"])
     return res
+
+
+PROFILE_KEYS = ("profile_counts", "profile_fits", "profile_kind", "line_points")
+PROFILE_COUNT_FIELDS = ("samples", "on_in", "on_glass", "on_depth", "a_in", "a_glass", "a_depth", "b_in", "b_glass", "b_depth",
+                        "region_a", "region_b")
+PROFILE_FIT_FIELDS = ("w0", "w1", "rms", "n_used", "status")
+PROFILE_PROBES = ("on", "a", "b")
+
+
+def profile_keys(intrinsics=False):
+    """The keys line_profiles returns without / with intrinsics."""
+    return PROFILE_KEYS if intrinsics else PROFILE_KEYS[:3]
+
+
+def check_line_profile_options(offset=3.0, max_samples=2048, min_depth=1e-3, max_depth=10.0, hi=700, lo=300):
+    """Host validation of line_profiles' options (also what InferenceSession(line_profiles=...) accepts); -> them as a dict."""
+    if not 0.0 < float(offset) <= 16384.0:
+        raise ValueError("line_profiles: 0 < offset <= 16384 pixels, got %r" % (offset,))
+    if int(max_samples) != max_samples or not 2 <= int(max_samples) <= hip.PROFILE_MAX_SAMPLES:
+        raise ValueError("line_profiles: 2 <= max_samples <= %d, got %r" % (hip.PROFILE_MAX_SAMPLES, max_samples))
+    if int(hi) != hi or int(lo) != lo or not 0 <= int(lo) < int(hi) <= 1000:
+        raise ValueError("line_profiles: 0 <= lo < hi <= 1000 per mille, got lo %r, hi %r" % (lo, hi))
+    if not 0.0 < float(min_depth) < float(max_depth):
+        raise ValueError("line_profiles: 0 < min_depth < max_depth, got %r, %r" % (min_depth, max_depth))
+    lo_mm, hi_mm = region_mm_range(min_depth, max_depth)
+    if lo_mm > hi_mm:
+        raise ValueError("line_profiles: no whole millimetre lies in [%r, %r] metres" % (min_depth, max_depth))
+    return dict(offset=float(offset), max_samples=int(max_samples), min_depth=float(min_depth), max_depth=float(max_depth),
+                hi=int(hi), lo=int(lo))
+
+
+def line_profiles(lines, count, labels, depth_mm, sizes, order=None, region_map=None, intrinsics=None, offset=3.0, max_samples=2048,
+                  min_depth=1e-3, max_depth=10.0, hi=700, lo=300):
+    """Every detected line walked through the dense results, on the device, in one launch (gwd_line_profiles):
+    lines (B,C,4) float64 or float32 (x1, y1, x2, y2) frame pixels and count (B,) int32 - nms_lines / nms_count, or lines / count
+    with order (B,C) int32 (row r reads lines[b, order[b, r]]) - and labels uint8 / depth_mm uint16 (B,Fh,Fw), sizes (B,2) int32 of
+    the same frames; region_map: glass_regions' map; intrinsics (B,4) float64 (fx, fy, cx, cy) at frame size.  B <= 16, sides <=
+    16384, C <= 2048.
+
+    A line of squared length L2 gets S = n + 1 samples at t = k / n, n = ceil(sqrt(L2)) (at most max_samples - 1), and every sample
+    three probes: on the line, and `offset` pixels to either side of it - a = on + offset (-dy, dx) / L, b = on - the same.  A probe
+    reads the pixel (floor x, floor y) of its own frame.
+    -> dict: profile_counts (B,C,12) int32 in PROFILE_COUNT_FIELDS order (per probe: in the frame, glass, with depth in
+    [min_depth, max_depth]; region_a / region_b: the rank of region_map most samples of that side lie in, -1 for none),
+    profile_fits (B,C,3,5) float64 per probe in PROFILE_FIT_FIELDS order: the least-squares fit of inverse depth 1000 / mm (1 / m),
+    affine in t - which is the 3-D line, 1 / Z being affine along the image of a segment - at t = 0 and t = 1, the rms of its
+    residual, the samples used and a status (0 fitted, 1 fewer than 2 samples with depth, 2 degenerate line, 3 a row from count on),
+    profile_kind (B,C) int32: 1 / 2 glass on side a / b only (at least hi per mille glass on one side, at most lo on the other),
+    3 both, 4 neither, 0 undecided; with intrinsics line_points (B,C,2,3) float64, the two ends in camera coordinates (NaN without
+    a fit).  Rows from count on hold 0, regions -1, status 3.  Fresh tensors, no host sync; repeated calls are bit-identical."""
+    opt = check_line_profile_options(offset, max_samples, min_depth, max_depth, hi, lo)
+    if not torch.is_tensor(lines) or lines.dtype not in (torch.float32, torch.float64):
+        raise TypeError("line_profiles: lines must be a float32 or float64 tensor")
+    for name, t, dt in (("count", count, torch.int32), ("labels", labels, torch.uint8), ("depth_mm", depth_mm, torch.uint16),
+                        ("sizes", sizes, torch.int32), ("order", order, torch.int32), ("region_map", region_map, torch.uint8),
+                        ("intrinsics", intrinsics, torch.float64)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dt):
+            raise TypeError("line_profiles: %s must be a %s tensor" % (name, dt))
+    if labels.dim() != 3 or 0 in labels.shape or lines.dim() != 3 or lines.shape[2] != 4 or lines.shape[1] == 0:
+        raise ValueError("line_profiles: labels must be (B, Fh, Fw) and lines (B, C, 4), got %s, %s" % (tuple(labels.shape), tuple(lines.shape)))
+    B, Fh, Fw = labels.shape
+    C = lines.shape[1]
+    if B > hip.AUGMENT_BATCH or max(Fh, Fw) > 16384 or C > hip.PROFILE_MAX_LINES:
+        raise ValueError("line_profiles: at most %d frames of at most 16384 per side and %d lines each, got %s, %s"
+                         % (hip.AUGMENT_BATCH, hip.PROFILE_MAX_LINES, tuple(labels.shape), tuple(lines.shape)))
+    if lines.shape[0] != B or tuple(count.shape) != (B,) or tuple(depth_mm.shape) != (B, Fh, Fw) or tuple(sizes.shape) != (B, 2) \
+            or (order is not None and tuple(order.shape) != (B, C)) or (region_map is not None and tuple(region_map.shape) != (B, Fh, Fw)) \
+            or (intrinsics is not None and tuple(intrinsics.shape) != (B, 4)):
+        raise ValueError("line_profiles: operands do not fit (B, C, Fh, Fw) = %s" % ((B, C, Fh, Fw),))
+    dev = labels.device
+    c = lambda t: None if t is None else t.contiguous()
+    lo_mm, hi_mm = region_mm_range(opt["min_depth"], opt["max_depth"])
+    res = {"profile_counts": torch.empty((B, C, hip.PROFILE_COUNTS), dtype=torch.int32, device=dev),
+           "profile_fits": torch.empty((B, C, 3, 5), dtype=torch.float64, device=dev),
+           "profile_kind": torch.empty((B, C), dtype=torch.int32, device=dev)}
+    if intrinsics is not None:
+        res["line_points"] = torch.empty((B, C, 2, 3), dtype=torch.float64, device=dev)
+    _lib().line_profiles(c(lines), c(count), c(order), c(labels), c(depth_mm), c(sizes), c(region_map), c(intrinsics), opt["offset"],
+                         opt["max_samples"], lo_mm, hi_mm, opt["hi"], opt["lo"], res["profile_counts"], res["profile_fits"],
+                         res["profile_kind"], res.get("line_points"))
+    return res

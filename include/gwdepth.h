@@ -966,6 +966,41 @@ int gwd_depth_planar(const uint8_t *region_map, const uint16_t *depth_mm, const 
                      const int32_t *region_count, const double *planes, int32_t B, int32_t Fh, int32_t Fw, int32_t max_regions,
                      float min_depth, float max_depth, float *depth_planar, uint16_t *depth_planar_mm, void *stream);
 
+/* Line profiles (csrc/lineprofile.hip, the scalar geometry is csrc/lineprobe.h): every detected line walked
+ * through the dense results of the same frames, in ONE launch, one wave per line.  lines [B][C][4] fp32 (GWD_LINES_F32) or fp64
+ * (GWD_LINES_F64) (x1, y1, x2, y2) frame pixels; count [B] int32: rows r < count[b] are processed (clamped to 0 .. C); order [B][C]
+ * int32 or NULL: row r reads lines[b][order[b][r]] (an index outside 0 .. C-1 makes the row degenerate).  labels / depth_mm / sizes
+ * as for gwd_glass_regions; region_map [B][Fh][Fw] uint8 of gwd_glass_regions or NULL; intrinsics [B][4] fp64 (fx, fy, cx, cy) and
+ * line_points, both or neither.  B <= 16, Fh, Fw <= 16384, C <= GWD_PROFILE_MAX_LINES.  All arithmetic is fp64, every operation
+ * rounded on its own.  With dx = x2 - x1, dy = y2 - y1, L2 = dx dx + dy dy:
+ *   samples   n = the smallest integer >= 1 with n n >= L2, at most max_samples - 1 (2 <= max_samples <= GWD_PROFILE_MAX_SAMPLES);
+ *             S = n + 1 samples at t = k / n.  L2 not a positive finite number: a degenerate line.
+ *   probes    per sample `on` = (x1 + t dx, y1 + t dy), a = on + offset (-dy / L, dx / L), b = on - the same; a probe reads the
+ *             pixel (floor x, floor y) and is in the frame iff 0 <= x < fw, 0 <= y < fh of its image.
+ *   counts    [B][C][GWD_PROFILE_COUNTS] int32: S; n_in, n_glass (label 1), n_depth (lo_mm <= mm <= hi_mm) of on, a, b; region_a,
+ *             region_b = the rank of region_map holding most in-frame samples of that side (ties: the lower rank), -1 for none.
+ *   fits      [B][C][3][5] fp64 per probe: w0, w1 (the least-squares fit of w = 1000 / mm, affine in t, at t = 0 and 1; centred,
+ *             two passes), rms of the residual (third pass), n_used, status: 0 fitted, 1 fewer than 2 samples with depth (NaN),
+ *             2 degenerate line (NaN, every count 0), 3 a row from count[b] on (zeros, regions -1, kind 0).
+ *   kind      [B][C] int32.  A side has glass when 1000 n_glass >= hi n_in, has none when 1000 n_glass <= lo n_in (n_in > 0,
+ *             0 <= lo < hi <= 1000): 1 glass on side a only, 2 on side b only, 3 on both, 4 on neither, 0 anything else.
+ *   line_points [B][C][2][3] fp64: the ends ((x - cx) / fx, (y - cy) / fy, 1) z with z = 1 / w, w = w0, w1 of the `on` fit; NaN
+ *             where that fit has status != 0 (rows from count[b] on included) or w <= 0.
+ * No global atomics, no memset, no floating-point atomics; bit-identical from call to call; a line's record depends on neither
+ * its row nor its neighbours nor Fh x Fw.  -1 on a null pointer or a size / range outside its limits (offset in (0, 16384]),
+ * -2 on another lines_dtype, C > GWD_PROFILE_MAX_LINES or max_samples outside 2 .. GWD_PROFILE_MAX_SAMPLES, -3 when a pointer is
+ * not aligned to its element; nothing is launched then.                                                                       */
+#define GWD_LINES_F32 0
+#define GWD_LINES_F64 1
+#define GWD_PROFILE_MAX_LINES 2048
+#define GWD_PROFILE_MAX_SAMPLES 2048
+#define GWD_PROFILE_COUNTS 12
+int gwd_line_profiles(const void *lines, int32_t lines_dtype, const int32_t *count, const int32_t *order, const uint8_t *labels,
+                      const uint16_t *depth_mm, const int32_t *sizes, const uint8_t *region_map, const double *intrinsics,
+                      int32_t B, int32_t C, int32_t Fh, int32_t Fw, double offset, int32_t max_samples, int32_t lo_mm,
+                      int32_t hi_mm, int32_t hi, int32_t lo, int32_t *counts, double *fits, int32_t *kind, double *line_points,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
