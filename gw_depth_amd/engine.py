@@ -19,18 +19,15 @@ optimizer / DDP setup of /root/reference/src/main_glassrgbd.py:46-67, re-laid fo
   k+1 runs, so the gradient all-reduce overlaps with backward in the replayed step as well.
 """
 import contextlib
-import gc
 import math
-import os
-import warnings
-from collections import OrderedDict
 
 import torch
 import torch.distributed as dist
 
-from . import hip, ops
+from . import graphs, hip, ops
+from .graphs import GraphCache      # noqa: F401 - `from gw_depth_amd.engine import GraphCache` keeps working; the class lives in graphs.py
 from .health import HealthState
-from .criteria import PackedTargets, target_capacity
+from .criteria import PackedTargets, pack_targets, target_capacity
 from .model import NestedTensor
 
 FORWARD_ORDER = ["backbone", "input_proj", "query_embed", "transformer", "class_embed", "lines_embed",
@@ -46,66 +43,19 @@ def never_used(name):
     parity: glassrgbd.py / multiscale_transformerr.py build them, no forward reads them; the 1/32 depth map feeds only the
     gradient-free CertainSample).  A wrong answer here costs overlap, never correctness: see TrainStep._bucket_ready."""
     return any(k in name for k in NEVER_USED) or ("class_transformer" in name and (".diff_mu" in name or ".diff_logsigma" in name))
-MAX_GRAPHS = 6          # captured batch signatures kept (least recently used goes first); all share one memory pool
-
-
-class GraphCache:
-    """Which batch signatures of a graph-mode TrainStep hold a captured step: pure bookkeeping, no device.
-
-    `entries` is the least-recently-used ordered table of the signatures that have been through a capture attempt (captured, or
-    refused: {"graph": None, ...}); `seen` counts the sights of the signatures still waiting.  A signature is captured at its `capture_after`-th
-    sight and runs eagerly before that, so a shape that shows up once in an epoch never pays the warm-up passes of a capture.  The
-    bound is `max_graphs`, or the module's MAX_GRAPHS read at every call when it is None."""
-    COUNTERS = ("replays", "captures", "eager_steps", "evictions", "refused", "host_matcher_steps")
-    SEEN_MAX = 4096         # waiting signatures remembered
-
-    def __init__(self, max_graphs=None, capture_after=1):
-        if max_graphs is not None and int(max_graphs) < 1:
-            raise ValueError("max_graphs must be >= 1, got %r" % (max_graphs,))
-        if int(capture_after) < 1:
-            raise ValueError("capture_after must be >= 1, got %r" % (capture_after,))
-        self.max_graphs = None if max_graphs is None else int(max_graphs)
-        self.capture_after = int(capture_after)
-        self.entries = OrderedDict()
-        self.seen = {}
-        self.stats = dict.fromkeys(self.COUNTERS, 0)
-
-    def bound(self):
-        return MAX_GRAPHS if self.max_graphs is None else self.max_graphs
-
-    def lookup(self, key):
-        """One sight of `key` -> ("known", entry): it has been through a capture attempt (entry["graph"] is None if that was refused)
-        and is the most recently used now; ("wait", None): run it eagerly; ("capture", None): capture it now and store() the entry."""
-        ent = self.entries.get(key)
-        if ent is not None:
-            self.entries.move_to_end(key)
-            return "known", ent
-        n = self.seen.pop(key, 0) + 1                  # re-inserted at the young end
-        if n >= self.capture_after:
-            return "capture", None                     # its count is dropped: an evicted signature starts over
-        self.seen[key] = n
-        while len(self.seen) > self.SEEN_MAX:          # waiting signatures are bounded too: the one not seen for longest goes
-            del self.seen[next(iter(self.seen))]
-        return "wait", None
-
-    def make_room(self):
-        """Drop least recently used entries until one more fits; called BEFORE a capture, so the executables go first."""
-        while len(self.entries) >= max(self.bound(), 1):
-            self.entries.popitem(last=False)
-            self.stats["evictions"] += 1
-
-    def store(self, key, ent):
-        self.make_room()
-        self.entries[key] = ent
-        self.stats["captures" if ent.get("graph") is not None else "refused"] += 1
-        return ent
-
-    def count(self, name, n=1):
-        self.stats[name] += n
 
 
 def _align(n):
     return (n + ALIGN - 1) // ALIGN * ALIGN
+
+
+def static_batch(batch, device=None, cap=None):
+    """A collated batch as the static tensors TrainStep._sync_free_fb takes: copies of images, pad_mask, depth and seg on `device`
+    (the batch's own unless given) and the targets as criteria.PackedTargets of capacity `cap` (their own size class unless given)."""
+    dev = batch["images"].device if device is None else torch.device(device)
+    st = {k: batch[k].to(dev, copy=True) for k in ("images", "pad_mask", "depth", "seg")}
+    st["packed"] = pack_targets(batch["targets"], dev, cap)
+    return st
 
 
 class TrainStep:
@@ -132,10 +82,9 @@ class TrainStep:
         self.device_matcher = True        # gwd_lsap + sync-free criterion (taps / teacher-forced tests use the host matcher)
         self._packs = {}                  # (batch size, capacity) -> PackedTargets of the eager path
         self.use_graph = bool(graph)      # capture zero_grad+forward+losses+backward of a batch signature as a chain of HIP graphs
-        self._cache = GraphCache(max_graphs, capture_after)     # which signatures are captured, and the counters of graph_stats()
+        self._cache = graphs.GraphCache(max_graphs, capture_after)     # which signatures are captured, and the counters of graph_stats()
         self._graphs = self._cache.entries                      # signature -> {"graph": chain or None, ...}, least recently used first
-        self._pool = None
-        self._gstream = None
+        self._side = graphs.GraphSide()                         # the stream and the memory pool of every graph-mode pass
         self._pending_checks = []
         self._pending_health = []         # guard="skip": control blocks on their way to the host, examined one step late
         self._health_seen = None          # the newest one examined
@@ -554,20 +503,14 @@ class TrainStep:
                 raise FloatingPointError("%d optimizer steps in a row skipped for non-finite gradients (step %d, %d elements in the last); "
                                          "tensors: %r" % (h["streak"], step_no, h["last"]["nonfinite_total"], self.first_nonfinite()))
 
-    def forward_backward(self, batch, taps=None):
-        """Forward, losses, backward and (N > 1) the bucketed gradient all-reduce; leaves SUMMED grads in flat_g."""
-        self._not_in_ema("forward_backward")
+    def _fb(self, b, targets, packed, taps=None, match=None):
+        """The one forward/backward: the weight-cache pass around forward, 17 losses, zero_grad and backward with its two queues and
+        the bucket bookkeeping.  b: images, pad_mask, depth, seg (a batch or a static batch) -> (out, total, terms), attached."""
         self.model.train()
-        packed = self._packed(batch["targets"]) if self.device_matcher else None
-        if packed is None:
-            self._cache.count("host_matcher_steps")
-        match = (self.criterion.matcher, batch["targets"]) if (packed is None and hasattr(self.criterion.matcher, "prefetch")) else None
-        weights = self.weights if (self.compute_dtype == torch.bfloat16 and batch["images"].is_cuda) else None
-        if weights is not None:
-            weights.begin_pass()
-        try:
-            out = self.model(NestedTensor(batch["images"], batch["pad_mask"]), taps=taps, match=match)
-            total, terms = self.losses(out, batch["depth"], batch["seg"], batch["targets"], packed=packed)
+        cached = self.compute_dtype == torch.bfloat16 and b["images"].is_cuda
+        with (self.weights if cached else contextlib.nullcontext()):      # every transposed / BN-folded bf16 weight copy, one launch
+            out = self.model(NestedTensor(b["images"], b["pad_mask"]), taps=taps, match=match)
+            total, terms = self.losses(out, b["depth"], b["seg"], targets, packed=packed)
             self.zero_grad()
             self._begin_backward()
             try:
@@ -577,156 +520,64 @@ class TrainStep:
                 self._state = None
                 raise
             self._finish_backward()
-        finally:
-            if weights is not None:
-                weights.end_pass()
         return out, total, terms
+
+    def forward_backward(self, batch, taps=None):
+        """Forward, losses, backward and (N > 1) the bucketed gradient all-reduce; leaves SUMMED grads in flat_g."""
+        self._not_in_ema("forward_backward")
+        packed = self._packed(batch["targets"]) if self.device_matcher else None
+        if packed is None:
+            self._cache.count("host_matcher_steps")
+        match = (self.criterion.matcher, batch["targets"]) if (packed is None and hasattr(self.criterion.matcher, "prefetch")) else None
+        return self._fb(batch, batch["targets"], packed, taps, match)
 
     # ------------------------------------------------------------------ HIP-graph path (no host sync inside)
     def _sync_free_fb(self, st):
-        """zero_grad + forward + 17 losses + backward on the static tensors `st`; contains no host round trip
+        """zero_grad + forward + 17 losses + backward on the static tensors `st` (static_batch); contains no host round trip
         (device LSAP, device CertainSample, fused losses) and no collective, hence capturable."""
-        self.model.train()
-        weights = self.weights if (self.compute_dtype == torch.bfloat16 and st["images"].is_cuda) else None
-        if weights is not None:
-            weights.begin_pass()                       # every transposed / BN-folded bf16 weight copy, one launch
-        try:
-            out = self.model(NestedTensor(st["images"], st["pad_mask"]), taps=st.get("taps"))
-            total, terms = self.losses(out, st["depth"], st["seg"], None, packed=st["packed"])
-            self.flat_g.zero_()
-            self._begin_backward()
-            try:
-                with ops.COLSUMS, ops.WGRADS:
-                    total.backward()
-            except BaseException:
-                self._state = None
-                raise
-            self._finish_backward()
-        finally:
-            if weights is not None:
-                weights.end_pass()
+        out, total, terms = self._fb(st, None, st["packed"], st.get("taps"))
         return out, total.detach(), {k: v.detach() for k, v in terms.items()}
 
     def _graph_stream(self):
-        """The one non-default stream every graph-mode forward/backward of this TrainStep runs on.  autograd binds
-        each parameter's AccumulateGrad node to the stream it was created under and keeps it as long as any autograd
-        graph referencing it is alive; if such a node predates the capture on another stream, its in-place gradient
-        accumulation is captured on a forked branch whose input buffers the allocator recycles without ordering."""
-        if self._gstream is None:
-            self._gstream = torch.cuda.Stream()
-        return self._gstream
+        return self._side.stream()
 
     def _count_memsets(self, st):
-        """Run one sync-free pass under the profiler and count the hipMemsetAsync runtime calls it makes."""
-        from torch.profiler import ProfilerActivity, profile
+        return graphs.count_memsets(lambda: self._sync_free_fb(st))
+
+    def _captured_pass(self, st, cut):
+        """One sync-free pass for graphs.GraphSide.attempt: a warm-up pass (cut is None), or the captured one, whose chain is cut
+        wherever buckets become ready - with bucket hooks installed (world > 1) in the middle of backward, without them never."""
+        self._cut = cut
         try:
-            with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-                self._sync_free_fb(st)
-                torch.cuda.synchronize()
-            return sum(1 for e in prof.events() if e.name == "hipMemsetAsync")
-        except Exception as exc:                     # no tracer on this host: without the audit there is no capture
-            warnings.warn("gw_depth_amd: capture audit unavailable (%s)" % exc)
+            return self._sync_free_fb(st)
+        except RuntimeError:
             self._state = None
-            self._sync_free_fb(st)
-            return -1
-
-    def _capture(self, st):
-        """Capture one sync-free pass as a chain of HIP graphs on the graph stream -> [(graph, bucket ids to all-reduce once
-        it has been enqueued)].  With bucket hooks installed (world > 1) the chain is cut whenever buckets become ready:
-        the hook ends the running capture and begins the next one on the same stream and memory pool, in the middle of
-        backward (autograd runs single-threaded here, so begin and end happen on one thread, which thread-local capture
-        mode requires).  Without hooks it is one graph."""
-        side = self._graph_stream()
-        if self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
-        chain, cur = [], [None]
-
-        def begin():
-            g = torch.cuda.CUDAGraph()
-            # thread_local: RCCL's watchdog / proxy threads may touch the runtime while this thread captures
-            g.capture_begin(pool=self._pool, capture_error_mode="thread_local")
-            cur[0] = g
-
-        def cut(bucket_ids, final):
-            cur[0].capture_end()
-            chain.append((cur[0], list(bucket_ids)))
-            cur[0] = None
-            if not final:                              # the last buckets close the step: nothing is enqueued after them
-                begin()
-
-        torch.cuda.synchronize()
-        gc.collect()
-        res = None
-        try:
-            with torch.cuda.stream(side), torch.autograd.set_multithreading_enabled(False):
-                begin()
-                self._cut = cut
-                try:
-                    res = self._sync_free_fb(st)
-                finally:
-                    self._cut = None
-                    if cur[0] is not None:
-                        cur[0].capture_end()
-                        chain.append((cur[0], []))
-                        cur[0] = None
+            raise
         finally:
-            self._works = []
-        return chain, res
+            self._cut = None
+            if cut is not None:
+                self._works = []
 
     def _graph_entry(self, batch):
         sizes = [int(len(t["labels"])) for t in batch["targets"]]
         if not self._device_matchable(sizes):
             return None                                # device LSAP limits: this batch runs eagerly with the host matcher
         key = (tuple(batch["images"].shape), target_capacity(sum(sizes)))
-        cache = self._cache
-        verdict, ent = cache.lookup(key)
+        verdict, ent = self._cache.lookup(key)
         if verdict != "capture":
             return ent                                 # a hit, or None: the signature runs eagerly until its capture_after-th sight
-        cache.make_room()                              # bounded cache; the executables go, the shared pool keeps the memory
-        dev = self.flat_p.device
-        st = {k: batch[k].clone() for k in ("images", "pad_mask", "depth", "seg")}
-        st["packed"] = PackedTargets(len(sizes), key[1], dev).update(batch["targets"])
-        side = self._graph_stream()
-        side.wait_stream(torch.cuda.current_stream())
         launch, self._launch = self._launch, (lambda bi: None)     # warm-up passes and capture issue NO collective
         try:
-            with torch.cuda.stream(side), warnings.catch_warnings(record=True) as caught:
-                warnings.simplefilter("always")
-                self._sync_free_fb(st)                     # allocator / lazily built caches / AccumulateGrad nodes / hook counts
-                memsets = self._count_memsets(st)          # second warm-up pass, audited
-            torch.cuda.current_stream().wait_stream(side)
-            reason = None
-            if any("AccumulateGrad node's stream does not match" in str(w.message) for w in caught):
-                reason = ("an autograd graph built on another stream is still alive (e.g. the outputs of an eager step): its "
-                          "AccumulateGrad nodes would be captured on a forked stream")
-            elif memsets < 0:
-                reason = "the capture audit (torch.profiler runtime-call trace) is not available on this host"
-            elif memsets:
-                reason = ("%d hipMemsetAsync call(s) in the step (ATen multi-block reductions zero their semaphores that way); "
-                          "memset nodes do not replay correctly in HIP graphs on this ROCm" % memsets)
-            if reason is not None:
-                warnings.warn("gw_depth_amd: HIP-graph capture refused for batch signature %r, running eager: %s" % (key, reason))
-                return cache.store(key, {"graph": None, "reason": reason})
-            try:
-                chain, res = self._capture(st)
-            except RuntimeError as e:                   # capture invalidated: keep training, eagerly, and say so
-                torch.cuda.synchronize()
-                self._state = None
-                warnings.warn("gw_depth_amd: HIP-graph capture failed for batch signature %r, running eager: %s" % (key, e))
-                return cache.store(key, {"graph": None, "reason": str(e)})
+            return self._side.attempt(self._cache, key, lambda: static_batch(batch, self.flat_p.device, key[1]), self._captured_pass,
+                                      lambda st: self._count_memsets(st), "batch", "step", record=True, single_thread=True)
         finally:
             self._launch = launch
-        return cache.store(key, {"graph": chain, "static": st, "result": res})
 
     def _on_graph_stream(self, batch, taps):
-        """Eager forward/backward of a graph-mode TrainStep: same stream as the captures (see _graph_stream), and the same
+        """Eager forward/backward of a graph-mode TrainStep: same stream as the captures (graphs.GraphSide.stream), and the same
         collective sequence as a replayed step (one num_items all-reduce, then every bucket once, in index order)."""
-        side = self._graph_stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            res = self.forward_backward(batch, taps)
-        torch.cuda.current_stream().wait_stream(side)
-        return res
+        with self._side.handover():
+            return self.forward_backward(batch, taps)
 
     def _graph_step(self, batch):
         ent = self._graph_entry(batch)

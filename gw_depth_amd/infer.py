@@ -6,20 +6,18 @@ launches every kernel from Python and ends at raw tensors.  An InferenceSession
 * freezes the weight copies: it owns an ops.WeightCache(frozen=True) over the storage of every parameter and buffer, so a
   copy is made when its weight is first seen (the first call) and stays; refresh() rewrites all of them in place with one launch;
 * replays a captured HIP graph per input signature (B, H, W): forward and post-processing, on one private stream, out of one
-  memory pool, least recently used signature dropped beyond engine.MAX_GRAPHS;
+  memory pool, least recently used signature dropped beyond graphs.MAX_GRAPHS;
 * finishes on the device: the un-padded sizes from the pad mask, the dense post-processing (gwd_dense_postprocess), the line
   post-processing with a ranking (gwd_line_postprocess) and - where asked for (line_nms=) - L-CNN's line NMS over the queries
   (gwd_line_nms), all inside the captured graph, no host sync anywhere.
 """
 import contextlib
-import gc
-import warnings
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from . import data, engine, hip, ops
+from . import data, graphs, hip, ops
 from .model import NestedTensor, nested_tensor_from_tensor_list
 
 RESULT_KEYS = ("depth", "depth_mm", "labels", "scores", "lines", "order", "count", "sizes")
@@ -28,21 +26,6 @@ _REGION_OPTIONS = ("max_regions", "min_area", "connectivity", "min_depth", "max_
 REGION_KEYS = ops.REGION_KEYS                                          # added to predict_frames' result by a session built with regions=
 _PROFILE_OPTIONS = ("offset", "max_samples", "min_depth", "max_depth", "hi", "lo")
 PROFILE_KEYS = ops.PROFILE_KEYS                                        # ... with line_profiles= (line_points only when intrinsics are passed)
-
-
-def _count_memsets_in(fn):
-    """Run fn() under the profiler and count the hipMemsetAsync runtime calls it makes (the audit of TrainStep._count_memsets:
-    memset nodes do not replay correctly in HIP graphs on this ROCm).  -1: no tracer on this host, fn() has still run once."""
-    from torch.profiler import ProfilerActivity, profile
-    try:
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        return sum(1 for e in prof.events() if e.name == "hipMemsetAsync")
-    except Exception as exc:
-        warnings.warn("gw_depth_amd: capture audit unavailable (%s)" % exc)
-        fn()
-        return -1
 
 
 class InferenceSession:
@@ -55,7 +38,7 @@ class InferenceSession:
     `samples`: NestedTensor, (B,3,H,W) tensor or list of (3,h,w) tensors.  A call leaves the model in eval mode.
 
     LIFETIME OF OUTPUTS.  With graph=True the results of a replayed signature are the graph's static tensors: they are valid
-    until the next call with the same signature (B, H, W), which overwrites them in place (or until more than engine.MAX_GRAPHS
+    until the next call with the same signature (B, H, W), which overwrites them in place (or until more than graphs.MAX_GRAPHS
     other signatures have pushed it out of the cache).  Clone what must live longer, or use
     predict(..., copy=True), which returns fresh tensors.  Eager calls (graph=False, a call with taps, a refused capture)
     return fresh tensors anyway.
@@ -125,9 +108,9 @@ class InferenceSession:
                             % (sorted(set(line_profiles) - set(_PROFILE_OPTIONS)), ", ".join(_PROFILE_OPTIONS)))
         self.line_profiles = None if line_profiles is None else ops.check_line_profile_options(
             **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(line_profiles if isinstance(line_profiles, dict) else {})))
-        self._graphs = OrderedDict()
-        self._pool = None
-        self._gstream = None
+        self._cache = graphs.GraphCache()                  # every signature is captured at its first sight
+        self._graphs = self._cache.entries                 # signature -> {"graph": chain of one, or None, ...}, least recently used first
+        self._side = graphs.GraphSide()
         self._addr = self._addresses()
         spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in self._storage() if t.numel()]
         # built inside TrainStep.use_ema(): the averaged weights leave the parameters when that block ends, so the session keeps a copy
@@ -201,15 +184,11 @@ class InferenceSession:
             model.eval()
         keep = model.compute_dtype
         model.compute_dtype = self.compute_dtype
-        weights = self.weights if images.is_cuda else None
-        if weights is not None:
-            weights.begin_pass()
+        weights = self.weights if (self.weights is not None and images.is_cuda) else contextlib.nullcontext()
         try:
-            with torch.no_grad(), self._own_weights():
+            with weights, torch.no_grad(), self._own_weights():
                 return model(NestedTensor(images, mask), taps=taps)
         finally:
-            if weights is not None:
-                weights.end_pass()
             model.compute_dtype = keep
 
     def _post(self, out, mask, target, twin=0):
@@ -237,71 +216,23 @@ class InferenceSession:
         return out, self._post(out, st["mask"], st["target"], st["twin"])
 
     # ------------------------------------------------------------------ graphs
-    def _graph_stream(self):
-        if self._gstream is None:
-            self._gstream = torch.cuda.Stream()
-        return self._gstream
-
-    @contextlib.contextmanager
     def _on_stream(self):
-        """Everything a graph-mode session launches runs on its one private stream, ordered behind the caller's stream on the
-        way in and in front of it on the way out (no host sync).  An eager session stays on the caller's stream."""
-        if not (self.use_graph and torch.cuda.is_available()):
-            yield
-            return
-        side = self._graph_stream()
-        side.wait_stream(torch.cuda.current_stream())
-        try:
-            with torch.cuda.stream(side):
-                yield
-        finally:
-            torch.cuda.current_stream().wait_stream(side)
+        """Everything a graph-mode session launches runs on its one private stream (graphs.GraphSide.handover); an eager session
+        stays on the caller's stream."""
+        return self._side.handover(self.use_graph and torch.cuda.is_available())
 
     def _count_memsets(self, st):
-        return _count_memsets_in(lambda: self._pass(st))
+        return graphs.count_memsets(lambda: self._pass(st))
 
     def _graph_entry(self, images, mask, twin=0):
         key = tuple(int(images.shape[i]) for i in (0, 2, 3)) + (("twin",) if twin else ())
-        ent = self._graphs.get(key)
-        if ent is not None:
-            self._graphs.move_to_end(key)
+        verdict, ent = self._cache.lookup(key)
+        if verdict != "capture":
             return ent
-        while len(self._graphs) >= engine.MAX_GRAPHS:      # bounded cache; the executables go, the shared pool keeps the memory
-            self._graphs.popitem(last=False)
-        st = {"images": images.clone(), "mask": mask.clone(),
-              "target": torch.full((key[0], 2), -1, dtype=torch.int32, device=images.device), "twin": twin}
-        with self._on_stream():
-            self._pass(st)                                 # allocator, lazily built caches, the frozen weight copies
-            memsets = self._count_memsets(st)              # second warm-up pass, audited
-        reason = None
-        if memsets < 0:
-            reason = "the capture audit (torch.profiler runtime-call trace) is not available on this host"
-        elif memsets:
-            reason = ("%d hipMemsetAsync call(s) in the forward (ATen multi-block reductions zero their semaphores that way); "
-                      "memset nodes do not replay correctly in HIP graphs on this ROCm" % memsets)
-        if reason is not None:
-            warnings.warn("gw_depth_amd: HIP-graph capture refused for input signature %r, running eager: %s" % (key, reason))
-            ent = self._graphs[key] = {"graph": None, "reason": reason}
-            return ent
-        if self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
-        torch.cuda.synchronize()
-        gc.collect()
-        g = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.stream(self._graph_stream()):
-                g.capture_begin(pool=self._pool, capture_error_mode="thread_local")
-                try:
-                    res = self._pass(st)
-                finally:
-                    g.capture_end()
-        except RuntimeError as e:                          # capture invalidated: keep serving, eagerly, and say so
-            torch.cuda.synchronize()
-            warnings.warn("gw_depth_amd: HIP-graph capture failed for input signature %r, running eager: %s" % (key, e))
-            ent = self._graphs[key] = {"graph": None, "reason": str(e)}
-            return ent
-        ent = self._graphs[key] = {"graph": g, "static": st, "result": res}
-        return ent
+        static = lambda: {"images": images.clone(), "mask": mask.clone(),
+                          "target": torch.full((key[0], 2), -1, dtype=torch.int32, device=images.device), "twin": twin}
+        return self._side.attempt(self._cache, key, static, lambda st, cut: self._pass(st), lambda st: self._count_memsets(st),
+                                  "input", "forward")
 
     @property
     def graphs(self):
@@ -342,7 +273,8 @@ class InferenceSession:
                         st["target"].fill_(-1)
                     else:
                         st["target"].copy_(target, non_blocking=True)
-                    ent["graph"].replay()
+                    for g, _ in ent["graph"]:
+                        g.replay()
                 return ent["result"]
         with self._on_stream():
             out = self._forward(images, mask, taps=taps)

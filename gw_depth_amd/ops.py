@@ -26,7 +26,7 @@ def _lib():
 class WeightCache:
     """bf16 kernel-side copies of the conv / linear weights (row-scaled forward copy for folded FrozenBN, transposed
     copy for the data gradient), refreshed by ONE gwd_weight_prep_batch launch per train step instead of one small
-    launch per layer.  engine.TrainStep owns one and brackets each forward/backward with begin_pass() / end_pass();
+    launch per layer.  engine.TrainStep owns one and runs each forward/backward inside `with cache:` (begin_pass() / end_pass());
     outside such a pass (plain ops calls, fp32 runs) every copy is made on the fly as before.  A weight first seen inside a pass is
     prepared on the fly and joins the table for the next pass.
 
@@ -143,6 +143,14 @@ class WeightCache:
         global _ACTIVE_WEIGHTS
         self.active = False
         _ACTIVE_WEIGHTS = None
+
+    def __enter__(self):
+        self.begin_pass()
+        return self
+
+    def __exit__(self, *exc):
+        self.end_pass()
+        return False
 
     def derived(self, w, tag, make):
         """Frozen mode: a weight-shaped tensor the forward derives from parameter w on every call (its zero-padded form), made
@@ -1577,8 +1585,8 @@ def window_attention(q, k, v, table, rel, region, windows_per_image, scale):
 class _RowAffineFn(torch.autograd.Function):
     """mu + exp(logsigma) * x with per-channel mu / logsigma (the reference tokens' re-parameterisation,
     multiscale_transformerr.py:289-292).  The parameter gradients are column sums over the rows: own colsum kernel straight into
-    the flat gradient buffer - ATen's multi-block reduction zeroes its semaphore with hipMemsetAsync once the row count grows
-    (batch 16), which a HIP graph cannot replay (engine.TrainStep refuses the capture)."""
+    the flat gradient buffer - ATen's multi-block reduction zeroes its semaphore with an asynchronous memset once the row count grows
+    (batch 16), which a HIP graph cannot replay (graphs.refusal: the capture is refused)."""
 
     @staticmethod
     def forward(ctx, x, mu, logsigma, sinks):

@@ -10,7 +10,7 @@ import warnings
 import pytest
 import torch
 
-from gw_depth_amd import engine, hip
+from gw_depth_amd import graphs, hip
 from gw_depth_amd.infer import RESULT_KEYS, InferenceSession
 from gw_depth_amd.model import NestedTensor
 from gw_depth_amd.synth import synth_batch
@@ -115,7 +115,7 @@ def test_replay_hygiene_second_shape_and_eviction(built, monkeypatch):
     assert worst(flatten(graph(NestedTensor(img0, msk0))), flatten(eager(NestedTensor(img0, msk0)))) <= bar
     assert graph._graphs[(2, 96, 128)]["graph"] is first                # going back replays the first
     assert list(graph.graphs) == [(1, 96, 128), (2, 96, 128)]
-    monkeypatch.setattr(engine, "MAX_GRAPHS", 2)                       # the bound, made small: a third signature evicts the oldest
+    monkeypatch.setattr(graphs, "MAX_GRAPHS", 2)                       # the bound, made small: a third signature evicts the oldest
     img2, msk2 = inputs(3, 96, 128, seed=85)
     assert worst(flatten(graph(NestedTensor(img2, msk2))), flatten(eager(NestedTensor(img2, msk2)))) <= bar
     assert list(graph.graphs) == [(2, 96, 128), (3, 96, 128)] and captured(graph), "capture was refused"

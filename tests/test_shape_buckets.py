@@ -1,12 +1,12 @@
-"""Shape buckets and the captured-step cache policy, on the CPU: data.bucket_shape / padded_size, engine.GraphCache (the pure
+"""Shape buckets and the captured-step cache policy, on the CPU: data.bucket_shape / padded_size, graphs.GraphCache (the pure
 bookkeeping of TrainStep's graph mode) and the shape census of the training augmentation that motivates both."""
 import functools
 
 import pytest
 
-from gw_depth_amd import engine
+from gw_depth_amd import graphs
 from gw_depth_amd.data import bucket_shape, padded_size
-from gw_depth_amd.engine import GraphCache
+from gw_depth_amd.graphs import GraphCache
 
 
 def _census_tool():
@@ -62,8 +62,8 @@ def test_cache_keeps_the_most_recently_used():
 
 def test_cache_bound_defaults_to_the_module_constant_at_call_time(monkeypatch):
     c = GraphCache()
-    assert c.bound() == engine.MAX_GRAPHS
-    monkeypatch.setattr(engine, "MAX_GRAPHS", 2)
+    assert c.bound() == graphs.MAX_GRAPHS
+    monkeypatch.setattr(graphs, "MAX_GRAPHS", 2)
     for k in "abc":
         _captured(c, k)
     assert list(c.entries) == ["b", "c"] and c.stats["evictions"] == 1

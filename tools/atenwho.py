@@ -5,20 +5,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from torch.profiler import profile, ProfilerActivity
 from gw_depth_amd import Config, build_model
-from gw_depth_amd.engine import TrainStep
+from gw_depth_amd.engine import TrainStep, static_batch
 from gw_depth_amd.synth import det_fill_, synth_batch
-from gw_depth_amd.criteria import pack_targets
 
 cfg = Config(device="cuda", dropout=0.1, log_depth_error=True)
 model, crits, _ = build_model(cfg)
 model.load_state_dict(det_fill_({k: v.detach().clone() for k, v in model.state_dict().items()}, seed=0))
 model.cuda(); crits[0].cuda()
 step = TrainStep(model, crits, cfg, compute_dtype=torch.bfloat16, check_finite=False)
-b = synth_batch(8, 480, 640, seed=1)
-batch = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in b.items()}
-batch["targets"] = [{k: v.cuda() for k, v in t.items()} for t in b["targets"]]
-st = {k: batch[k].clone() for k in ("images", "pad_mask", "depth", "seg")}
-st["packed"] = pack_targets(batch["targets"], "cuda")
+st = static_batch(synth_batch(8, 480, 640, seed=1), "cuda")
 def _scoped(name, fwd):
     def run(*a, **k):
         with torch.profiler.record_function("M:" + name):

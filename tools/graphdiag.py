@@ -4,7 +4,7 @@ import os, sys, re, collections, socket
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gw_depth_amd import Config, build_model
-from gw_depth_amd.engine import TrainStep
+from gw_depth_amd.engine import TrainStep, static_batch
 from gw_depth_amd.synth import det_fill_, synth_batch
 
 mode = sys.argv[1] if len(sys.argv) > 1 else "plain"
@@ -20,9 +20,7 @@ batch["targets"] = [{k: v.cuda() for k, v in t.items()} for t in b["targets"]]
 print("host", socket.gethostname(), torch.cuda.get_device_name(0), torch.version.hip, flush=True)
 
 # eager reference on the same static inputs (no optimizer step: weights stay fixed)
-from gw_depth_amd.criteria import pack_targets
-st = {k: batch[k].clone() for k in ("images", "pad_mask", "depth", "seg")}
-st["packed"] = pack_targets(batch["targets"], "cuda")
+st = static_batch(batch)
 es = torch.cuda.current_stream() if mode == "mismatch" else step._graph_stream()
 es.wait_stream(torch.cuda.current_stream())
 with torch.cuda.stream(es):
@@ -47,7 +45,7 @@ if dump:
             g = super().__new__(cls, *a, **k); return g
     _g0 = orig_graph.__init__
 ent = None
-import gw_depth_amd.engine as E
+import gw_depth_amd.graphs as E
 if dump:
     real = torch.cuda.CUDAGraph
     def mk():
@@ -79,7 +77,7 @@ ent = step._graph_entry(batch)
 E.torch.cuda.CUDAGraph = orig_graph
 torch.cuda.synchronize()
 if dump:
-    ent["graph"].debug_dump(dump)
+    ent["graph"][0][0].debug_dump(dump)
     txt = open(dump).read()
     print("dot bytes", len(txt))
     kinds = collections.Counter(re.findall(r'label="?\{?\s*\n?([A-Za-z_]+)', txt))
@@ -89,7 +87,8 @@ if dump:
         print("  ", m[:300])
 for r in range(3):
     step.flat_g.fill_(float("nan"))                       # anything the graph does not rewrite shows up
-    ent["graph"].replay()
+    for g, _ in ent["graph"]:
+        g.replay()
     torch.cuda.synchronize()
     tot = float(ent["result"][1]); g = step.flat_g
     nf = int((~torch.isfinite(g)).sum())

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Small row-wise launches of the step (LayerNorm forward / backward of the DETR and Swin token shapes), run under
-`rocprofv3 --kernel-trace --stats` to read kernel times (tools/rowbench.sh); 30 launches per shape, operands reused (L2-warm, as in the step)."""
+`rocprofv3 --kernel-trace --stats -- python3 tools/rowbench.py` to read kernel times; 30 launches per shape, operands reused (L2-warm, as in the step)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

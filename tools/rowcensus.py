@@ -6,18 +6,15 @@ import os, sys, collections
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gw_depth_amd import Config, build_model, hip
-from gw_depth_amd.engine import TrainStep
+from gw_depth_amd.engine import TrainStep, static_batch
 from gw_depth_amd.synth import det_fill_, synth_batch
-from gw_depth_amd.criteria import pack_targets
 
 cfg = Config(device="cuda", dropout=0.1, log_depth_error=True)
 model, crits, _ = build_model(cfg)
 model.load_state_dict(det_fill_({k: v.detach().clone() for k, v in model.state_dict().items()}, seed=0))
 model.cuda(); crits[0].cuda()
 step = TrainStep(model, crits, cfg, compute_dtype=torch.bfloat16, check_finite=False)
-b = synth_batch(8, 480, 640, seed=1)
-st = {k: b[k].cuda() for k in ("images", "pad_mask", "depth", "seg")}
-st["packed"] = pack_targets([{k: v.cuda() for k, v in t.items()} for t in b["targets"]], "cuda")
+st = static_batch(synth_batch(8, 480, 640, seed=1), "cuda")
 for _ in range(2):
     step._sync_free_fb(st)
 torch.cuda.synchronize()
