@@ -1,5 +1,6 @@
 // Metres -> the millimetres of the data set's depth PNGs (src/datasets/glassrgbd_norhint.py:273), shared by the dense
-// post-processing (postproc.hip) and the planar depth of the glass regions (regions.hip) so that the two agree bit for bit.
+// post-processing (postproc.hip), the planar depth of the glass regions (regions.hip) and the fused sensor depth (fusion.hip) so that
+// all of them agree bit for bit.
 #pragma once
 #include "common.h"
 

@@ -22,9 +22,11 @@
 //   cc_finish_kernel    the public records in rank order.
 // gwd_region_planes     moments in fixed pieces (row y belongs to workgroup y % nb, a wave owns 64 neighbours of a row), one
 //                       partial record per workgroup, folded in ascending order; solve; a second pass of the same shape for rms.
+//                       The fit itself is planefit.h, shared with fusion.hip.
 // gwd_depth_planar      the copy of the depth with the pixels of fitted regions rewritten.
 #include "common.h"
 #include "depthmm.h"
+#include "planefit.h"
 
 namespace {
 
@@ -34,7 +36,7 @@ constexpr int kMaxR = GWD_REGION_MAX;
 constexpr int kRec = GWD_REGION_RECORD;                   // int64 fields of a record
 constexpr int kRows = 16;                                 // rows one workgroup of the flatten, candidate and record passes walks
 constexpr int kPlaneBlocks = 64;                          // workgroups per image of the moment passes, at most
-constexpr int kNI = 6, kND = 4;                           // integer / fp64 moments of a partial record
+constexpr int kNI = kFitNI, kND = kFitND;                 // integer / fp64 moments of a partial record (planefit.h)
 enum { F_AREA = 0, F_X0, F_Y0, F_X1, F_Y1, F_ANCHOR, F_SX, F_SY, F_ND, F_SMM, F_MINMM, F_MAXMM };
 
 struct Layout {                                           // byte offsets into the workspace, every one a multiple of 16
@@ -377,12 +379,6 @@ struct PlaneArgs {
     int32_t B, Fh, Fw, max_regions, lo_mm, hi_mm, nb;
 };
 
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // RESID 0: the ten moments of every region, coordinates relative to the region's (x0, y0); 1: the sum of squared residuals
 template <int RESID>
 __global__ __launch_bounds__(kThreads) void plane_moments_kernel(const PlaneArgs a) {
@@ -424,48 +420,17 @@ __global__ __launch_bounds__(kThreads) void plane_moments_kernel(const PlaneArgs
                 todo &= ~__ballot(mine);
                 const double w = mine ? 1000.0 / (double)mm : 0.0;
                 if (RESID) {
-                    const double e = mine ? w - ((ca[r - 1] * (double)x + cb[r - 1] * (double)y) + cg[r - 1]) : 0.0;
-                    const double s = wave_sum_d(e * e);
-                    if (lane == 0) pd[wave][r - 1][0] += s;
+                    fit_add_residual(mine ? fit_residual(w, ca[r - 1], cb[r - 1], cg[r - 1], x, y) : 0.0, lane, pd[wave][r - 1]);
                 } else {
                     const long long dx = mine ? x - ox[r - 1] : 0, dy = mine ? y - oy[r - 1] : 0;
-                    const long long vi[kNI] = {mine ? 1 : 0, dx, dy, dx * dx, dx * dy, dy * dy};
-                    const double vd[kND] = {w, (double)dx * w, (double)dy * w, w * w};
-#pragma unroll
-                    for (int k = 0; k < kNI; ++k) {
-                        const long long s = wave_sum_ll(vi[k]);
-                        if (lane == 0) pi[wave][r - 1][k] += s;
-                    }
-#pragma unroll
-                    for (int k = 0; k < kND; ++k) {
-                        const double s = wave_sum_d(vd[k]);
-                        if (lane == 0) pd[wave][r - 1][k] += s;
-                    }
+                    fit_add_moments(mine, dx, dy, w, lane, pi[wave][r - 1], pd[wave][r - 1]);
                 }
             }
         }
     }
     __syncthreads();
     long long *out = a.partial + ((int64_t)b * kPlaneBlocks + blk) * kMaxR * (kNI + kND);
-    for (int k = threadIdx.x; k < kMaxR * (kNI + kND); k += kThreads) {           // the four waves in order; every entry written
-        const int r = k / (kNI + kND), q = k - r * (kNI + kND);
-        if (q < kNI) out[k] = (pi[0][r][q] + pi[1][r][q]) + (pi[2][r][q] + pi[3][r][q]);
-        else ((double *)out)[k] = (pd[0][r][q - kNI] + pd[1][r][q - kNI]) + (pd[2][r][q - kNI] + pd[3][r][q - kNI]);
-    }
-}
-
-typedef unsigned __int128 u128;
-__device__ __forceinline__ double to_double(u128 v) {      // two exact halves, one rounding each
-    return (double)(unsigned long long)(v >> 64) * 18446744073709551616.0 + (double)(unsigned long long)v;
-}
-// a * b of two 128-bit values as (high, low) 128-bit halves
-__device__ void mul128(u128 a, u128 b, u128 &hi, u128 &lo) {
-    const u128 mask = ((u128)1 << 64) - 1;
-    const u128 a0 = a & mask, a1 = a >> 64, b0 = b & mask, b1 = b >> 64;
-    const u128 p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
-    const u128 mid = (p00 >> 64) + (p01 & mask) + (p10 & mask);
-    lo = (p00 & mask) | (mid << 64);
-    hi = p11 + (p01 >> 64) + (p10 >> 64) + (mid >> 64);
+    fit_store_partial(pi, pd, out, kMaxR, threadIdx.x, kThreads);
 }
 
 // one wave per (region, image): folds the workgroups' partial records in ascending order, then one thread solves
@@ -483,15 +448,7 @@ __global__ __launch_bounds__(64) void plane_solve_kernel(const PlaneArgs a) {
         return;
     }
     const long long *part = a.partial + (int64_t)b * kPlaneBlocks * kMaxR * (kNI + kND) + r * (kNI + kND);
-    if (q < kNI) {
-        long long s = 0;
-        for (int k = 0; k < a.nb; ++k) s += part[(int64_t)k * kMaxR * (kNI + kND) + q];
-        si[q] = s;
-    } else if (q < kNI + kND) {
-        double s = 0.0;
-        for (int k = 0; k < a.nb; ++k) s += ((const double *)part)[(int64_t)k * kMaxR * (kNI + kND) + q];
-        sd[q - kNI] = s;
-    }
+    fit_fold(part, a.nb, (int64_t)kMaxR * (kNI + kND), q, si, sd);
     __syncthreads();
     if (q != 0) return;
     if (RESID) {
@@ -499,39 +456,13 @@ __global__ __launch_bounds__(64) void plane_solve_kernel(const PlaneArgs a) {
         return;
     }
     const long long *rec = a.records + ((int64_t)b * a.max_regions + r) * kRec;
-    const long long n = si[0], Sx = si[1], Sy = si[2];
-    const double nan = __builtin_nan("");
-    bool flat = n < 3;
-    u128 Dxx = 0, Dyy = 0;
-    __int128 Dxy = 0;
-    if (!flat) {                                          // n * Sxx - Sx^2 etc. are exact: coordinates < 2^14, n < 2^28
-        Dxx = (u128)n * (u128)si[3] - (u128)Sx * (u128)Sx;
-        Dyy = (u128)n * (u128)si[5] - (u128)Sy * (u128)Sy;
-        Dxy = (__int128)n * si[4] - (__int128)Sx * Sy;
-        const u128 axy = Dxy < 0 ? (u128)(-Dxy) : (u128)Dxy;
-        u128 h1, l1, h2, l2;
-        mul128(Dxx, Dyy, h1, l1);
-        mul128(axy, axy, h2, l2);
-        flat = h1 == h2 && l1 == l2;                      // the determinant is never negative (Cauchy-Schwarz): zero = collinear
-    }
-    if (flat) {
-        pl[0] = pl[1] = pl[2] = pl[3] = nan;
-        pl[4] = (double)n;
-        pl[5] = 1.0;
-        return;
-    }
-    const double dn = (double)n, dSx = (double)Sx, dSy = (double)Sy, Sw = sd[0];
-    const double dxx = to_double(Dxx), dyy = to_double(Dyy), dxy = Dxy < 0 ? -to_double((u128)(-Dxy)) : to_double((u128)Dxy);
-    const double dxw = dn * sd[1] - dSx * Sw, dyw = dn * sd[2] - dSy * Sw;
-    const double det = dxx * dyy - dxy * dxy;
-    const double alpha = (dyy * dxw - dxy * dyw) / det, beta = (dxx * dyw - dxy * dxw) / det;
-    const double gamma_rel = (Sw - alpha * dSx - beta * dSy) / dn;
-    pl[0] = alpha;
-    pl[1] = beta;
-    pl[2] = gamma_rel - alpha * (double)rec[F_X0] - beta * (double)rec[F_Y0];
-    pl[3] = nan;                                          // the residual pass writes it
-    pl[4] = dn;
-    pl[5] = 0.0;
+    const PlaneFit fit = fit_solve(si, sd, rec[F_X0], rec[F_Y0]);
+    pl[0] = fit.alpha;
+    pl[1] = fit.beta;
+    pl[2] = fit.gamma;
+    pl[3] = __builtin_nan("");                            // of a fitted plane the residual pass writes it
+    pl[4] = fit.n;
+    pl[5] = fit.flat ? 1.0 : 0.0;
 }
 
 // ------------------------------------------------------------------------------------------------ planar depth

@@ -370,16 +370,25 @@ class FrameMetrics:
 
 @torch.no_grad()
 def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size=1024, max_size=1024, pad_to=None, depth_bins=None,
-                    metrics=None, planar=False):
+                    metrics=None, planar=False, sensor=None, fused=False):
     """Scores the samples `indices` (default: all) of a dataset.FrameStore / StreamSource through session.predict_frames at the
     frames' own resolution: `batch` frames per call (at most 16, 8 with ensemble=True), one gwd_eval_frames launch behind each,
     no host sync before the closing copy.  A device-resident FrameStore hands its 16-bit depth planes over in place (record_gt).
     planar=True (a session built with regions= and its planar depth): the metrics are fed depth_planar - the depth with every fitted
     glass region projected onto its plane in inverse depth, the prior GW-Depth's ground truth on glass was built with - in place of
     depth; compare the glass rows of both runs.  Pixels outside the kept regions are the same in both.
+    fused=True (a session built with fusion=) with sensor=callable: sensor(indices) returns the RGB-D camera's depth planes of those
+    samples as predict_frames(sensor_depth=) takes them, and the metrics are fed depth_fused - the sensor's depth completed behind
+    glass - in place of depth.
     -> metrics.compute() plus "names": {sample index: name} for FrameMetrics.worst.  Pass `metrics` to keep the accumulator."""
     if planar and not (getattr(session, "regions", None) or {}).get("planar"):
         raise ValueError("evaluate_frames(planar=True) needs an InferenceSession built with regions= (and planar=True in it)")
+    if fused and planar:
+        raise ValueError("evaluate_frames: planar=True and fused=True score different depths; pick one")
+    if fused and getattr(session, "fusion", None) is None:
+        raise ValueError("evaluate_frames(fused=True) needs an InferenceSession built with fusion= (and regions=)")
+    if fused != (sensor is not None) or (sensor is not None and not callable(sensor)):
+        raise ValueError("evaluate_frames: fused=True and sensor=callable(indices) go together")
     indices = list(range(len(source))) if indices is None else [int(i) for i in indices]
     limit = hip.EVAL_FRAMES_BATCH // 2 if ensemble else hip.EVAL_FRAMES_BATCH
     if not 0 < int(batch) <= limit:
@@ -395,7 +404,11 @@ def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size
         else:
             frames = source.frames(idx)
             rgb, gt = [f[0] for f in frames], [(f[1], f[2]) for f in frames]
-        res = session.predict_frames(rgb, size=size, max_size=max_size, ensemble=ensemble, pad_to=pad_to)
+        if fused:
+            res = session.predict_frames(rgb, size=size, max_size=max_size, ensemble=ensemble, pad_to=pad_to, sensor_depth=sensor(idx))
+            res = dict(res, depth=res["depth_fused"])
+        else:
+            res = session.predict_frames(rgb, size=size, max_size=max_size, ensemble=ensemble, pad_to=pad_to)
         if planar:
             res = dict(res, depth=res["depth_planar"])
         metrics.update(res, gt, ids=idx)

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GWD_LIB") or os.path.join(_HERE, "libgwdepth_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3, 4
-WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS = 0, 1, 2, 3, 4, 5          # gwd_query_workspace ops
+WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS, WS_FUSION = 0, 1, 2, 3, 4, 5, 6          # gwd_query_workspace ops
 GATHER_CONV, GATHER_TRANSPOSED, GATHER_UPSAMPLED = 0, 1, 2
 RESAMPLE_BILINEAR_AC, RESAMPLE_NEAREST = 0, 1
 
@@ -45,6 +45,7 @@ ENTRY_POINTS = [
     "gwd_adamw_step_ema", "gwd_ema_swap",
     "gwd_glass_regions", "gwd_region_planes", "gwd_depth_planar",
     "gwd_line_profiles",
+    "gwd_fusion_ring", "gwd_fusion_planes", "gwd_fusion_depth",
 ]
 
 
@@ -131,6 +132,9 @@ AUGMENT_BATCH = 16        # frames per grouped augmentation launch
 REGION_MAX = 32           # GWD_REGION_MAX: kept regions per image, at most
 REGION_RECORD = 12        # GWD_REGION_RECORD: int64 fields of a region's record
 REGION_CANDIDATES = 8192  # GWD_REGION_CANDIDATES: default length of the candidate list per image
+FUSION_MAX_RING = 32      # GWD_FUSION_MAX_RING: widest ring around a region, pixels
+FUSION_PLANE = 12         # GWD_FUSION_PLANE: fp64 fields of a fusion plane
+FUSED_SENSOR, FUSED_PLANE, FUSED_NETWORK = 1, 2, 3        # GWD_FUSED_*: fused_source
 PROFILE_MAX_LINES = 2048      # GWD_PROFILE_MAX_LINES: rows per image of gwd_line_profiles
 PROFILE_MAX_SAMPLES = 2048    # GWD_PROFILE_MAX_SAMPLES: samples per line, at most
 PROFILE_COUNTS = 12           # GWD_PROFILE_COUNTS: int32 fields of a line's counts
@@ -322,6 +326,9 @@ class HipLibrary:
         L.gwd_region_planes.argtypes = [vp] * 5 + [i32] * 6 + [vp] * 3
         L.gwd_depth_planar.argtypes = [vp] * 6 + [i32] * 4 + [f32, f32] + [vp] * 3
         L.gwd_line_profiles.argtypes = [vp, i32] + [vp] * 7 + [i32] * 4 + [ctypes.c_double] + [i32] * 5 + [vp] * 5
+        L.gwd_fusion_ring.argtypes = [vp] * 6 + [i32] * 10 + [vp] * 4
+        L.gwd_fusion_planes.argtypes = [vp] * 5 + [i32] * 7 + [ctypes.c_double, i32, ctypes.c_double] + [vp] * 3
+        L.gwd_fusion_depth.argtypes = [vp] * 8 + [i32] * 6 + [f32, f32] + [vp] * 4
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1324,6 +1331,66 @@ class HipLibrary:
             _ptr(region_map), _ptr(depth_mm), _ptr(depth), _ptr(sizes), _ptr(region_count), _ptr(planes), B, Fh, Fw, R, float(dmin),
             float(dmax), _ptr(depth_planar), _ptr(depth_planar_mm),
             self._stream(region_map, depth_mm, depth, sizes, region_count, planes, depth_planar, depth_planar_mm)), "gwd_depth_planar")
+
+    def fusion_ring(self, labels, sensor_mm, depth_mm, sizes, region_map, region_count, max_regions, ring, gap, lo_mm, hi_mm, align,
+                    min_align, workspace, fusion_ring, fusion_scale):
+        """gwd_fusion_ring: labels / region_map uint8, sensor_mm / depth_mm uint16 (B,Fh,Fw), sizes (B,2) / region_count (B,) int32;
+        outputs fusion_ring uint8 (B,Fh,Fw), fusion_scale (B,4) float64; workspace: a uint8 tensor of
+        workspace_bytes(WS_FUSION, B, Fh, Fw) bytes."""
+        self._typed("gwd_fusion_ring", ((labels, torch.uint8), (sensor_mm, torch.uint16), (depth_mm, torch.uint16), (sizes, torch.int32),
+                                        (region_map, torch.uint8), (region_count, torch.int32), (workspace, torch.uint8),
+                                        (fusion_ring, torch.uint8), (fusion_scale, torch.float64)))
+        B, Fh, Fw = labels.shape
+        shape = (B, Fh, Fw)
+        if tuple(sensor_mm.shape) != shape or tuple(depth_mm.shape) != shape or tuple(region_map.shape) != shape \
+                or tuple(fusion_ring.shape) != shape or tuple(sizes.shape) != (B, 2) or region_count.numel() != B \
+                or tuple(fusion_scale.shape) != (B, 4) or workspace.numel() < self.workspace_bytes(WS_FUSION, B, Fh, Fw):
+            raise ValueError("gwd_fusion_ring: operand sizes do not match (B, Fh, Fw) = (%d, %d, %d)" % shape)
+        self._check(self.lib.gwd_fusion_ring(
+            _ptr(labels), _ptr(sensor_mm), _ptr(depth_mm), _ptr(sizes), _ptr(region_map), _ptr(region_count), B, Fh, Fw, int(max_regions),
+            int(ring), int(gap), int(lo_mm), int(hi_mm), int(bool(align)), int(min_align), _ptr(workspace), _ptr(fusion_ring),
+            _ptr(fusion_scale),
+            self._stream(labels, sensor_mm, depth_mm, sizes, region_map, region_count, workspace, fusion_ring, fusion_scale)),
+            "gwd_fusion_ring")
+
+    def fusion_planes(self, fusion_ring, sensor_mm, sizes, region_count, records, ring, lo_mm, hi_mm, trim, min_ring, max_rms, workspace,
+                      fusion_planes):
+        """gwd_fusion_planes: the ring and the workspace of fusion_ring in, fusion_planes (B,max_regions,12) float64 out; max_rms
+        None: no limit."""
+        self._typed("gwd_fusion_planes", ((fusion_ring, torch.uint8), (sensor_mm, torch.uint16), (sizes, torch.int32),
+                                          (region_count, torch.int32), (records, torch.int64), (workspace, torch.uint8),
+                                          (fusion_planes, torch.float64)))
+        B, Fh, Fw = fusion_ring.shape
+        R = records.shape[1]
+        if tuple(sensor_mm.shape) != (B, Fh, Fw) or tuple(sizes.shape) != (B, 2) or region_count.numel() != B \
+                or tuple(records.shape) != (B, R, REGION_RECORD) or tuple(fusion_planes.shape) != (B, R, FUSION_PLANE) \
+                or workspace.numel() < self.workspace_bytes(WS_FUSION, B, Fh, Fw):
+            raise ValueError("gwd_fusion_planes: operand sizes do not match (B, Fh, Fw, max_regions) = (%d, %d, %d, %d)" % (B, Fh, Fw, R))
+        self._check(self.lib.gwd_fusion_planes(
+            _ptr(fusion_ring), _ptr(sensor_mm), _ptr(sizes), _ptr(region_count), _ptr(records), B, Fh, Fw, R, int(ring), int(lo_mm),
+            int(hi_mm), float(trim), int(min_ring), float("inf") if max_rms is None else float(max_rms), _ptr(workspace),
+            _ptr(fusion_planes), self._stream(fusion_ring, sensor_mm, sizes, region_count, records, workspace, fusion_planes)),
+            "gwd_fusion_planes")
+
+    def fusion_depth(self, labels, sensor_mm, depth, sizes, region_map, region_count, fusion_planes, fusion_scale, lo_mm, hi_mm, dmin,
+                     dmax, depth_fused, depth_fused_mm, fused_source):
+        """gwd_fusion_depth: depth_fused float32 / depth_fused_mm uint16 / fused_source uint8 (B,Fh,Fw) out."""
+        self._typed("gwd_fusion_depth", ((labels, torch.uint8), (sensor_mm, torch.uint16), (depth, torch.float32), (sizes, torch.int32),
+                                         (region_map, torch.uint8), (region_count, torch.int32), (fusion_planes, torch.float64),
+                                         (fusion_scale, torch.float64), (depth_fused, torch.float32), (depth_fused_mm, torch.uint16),
+                                         (fused_source, torch.uint8)))
+        B, Fh, Fw = labels.shape
+        shape, R = (B, Fh, Fw), fusion_planes.shape[1]
+        if any(tuple(t.shape) != shape for t in (sensor_mm, depth, region_map, depth_fused, depth_fused_mm, fused_source)) \
+                or tuple(sizes.shape) != (B, 2) or region_count.numel() != B or tuple(fusion_planes.shape) != (B, R, FUSION_PLANE) \
+                or tuple(fusion_scale.shape) != (B, 4):
+            raise ValueError("gwd_fusion_depth: operand sizes do not match (B, Fh, Fw, max_regions) = (%d, %d, %d, %d)" % (B, Fh, Fw, R))
+        self._check(self.lib.gwd_fusion_depth(
+            _ptr(labels), _ptr(sensor_mm), _ptr(depth), _ptr(sizes), _ptr(region_map), _ptr(region_count), _ptr(fusion_planes),
+            _ptr(fusion_scale), B, Fh, Fw, R, int(lo_mm), int(hi_mm), float(dmin), float(dmax), _ptr(depth_fused), _ptr(depth_fused_mm),
+            _ptr(fused_source),
+            self._stream(labels, sensor_mm, depth, sizes, region_map, region_count, fusion_planes, fusion_scale, depth_fused,
+                         depth_fused_mm, fused_source)), "gwd_fusion_depth")
 
     def line_profiles(self, lines, count, order, labels, depth_mm, sizes, region_map, intrinsics, offset, max_samples, lo_mm, hi_mm,
                       hi, lo, counts, fits, kind, line_points):

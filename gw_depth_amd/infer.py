@@ -26,6 +26,8 @@ _REGION_OPTIONS = ("max_regions", "min_area", "connectivity", "min_depth", "max_
 REGION_KEYS = ops.REGION_KEYS                                          # added to predict_frames' result by a session built with regions=
 _PROFILE_OPTIONS = ("offset", "max_samples", "min_depth", "max_depth", "hi", "lo")
 PROFILE_KEYS = ops.PROFILE_KEYS                                        # ... with line_profiles= (line_points only when intrinsics are passed)
+_FUSION_OPTIONS = ("ring", "gap", "trim", "min_ring", "max_rms", "align", "min_align", "min_depth", "max_depth")
+FUSION_KEYS = ops.FUSION_KEYS                                          # ... with fusion=, by a call that passes sensor_depth=
 
 
 class InferenceSession:
@@ -77,11 +79,20 @@ class InferenceSession:
     under ensemble=True), without it the count[b] lines above score_thresh, reached through `order`.  predict_frames(intrinsics=)
     adds line_points, the ends in camera coordinates.  predict() does not take part.
 
+    SENSOR FUSION.  fusion=None (the default): nothing is allocated, predict_frames issues the launches and returns the keys it always
+    did.  fusion=True or a dict of ops.sensor_fusion's options (ring, gap, trim, min_ring, max_rms, align, min_align; min_depth /
+    max_depth default to the session's) needs regions=: predict_frames(sensor_depth=...) - the depth planes of an RGB-D camera,
+    uint16 millimetres, 0 = no reading, registered to the frames - also returns FUSION_KEYS: the sensor's depth with every glass
+    region rewritten to the plane fitted from the depth measured on its frame, the network's depth scaled to the sensor where no
+    plane can be fitted and in the sensor's holes, and where each pixel came from; computed behind the regions on the session's
+    stream, as fresh tensors, with no host sync.  A call without sensor_depth returns what it returns today.  predict() does not
+    take part.
+
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
 
     def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6,
-                 line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None, line_profiles=None):
+                 line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None, line_profiles=None, fusion=None):
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
         if line_nms_order not in ("score", "query"):
@@ -108,6 +119,14 @@ class InferenceSession:
                             % (sorted(set(line_profiles) - set(_PROFILE_OPTIONS)), ", ".join(_PROFILE_OPTIONS)))
         self.line_profiles = None if line_profiles is None else ops.check_line_profile_options(
             **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(line_profiles if isinstance(line_profiles, dict) else {})))
+        if fusion is not None and fusion is not True and not isinstance(fusion, dict):
+            raise TypeError("fusion must be None, True or a dict of ops.sensor_fusion's options, got %r" % (fusion,))
+        if isinstance(fusion, dict) and set(fusion) - set(_FUSION_OPTIONS):
+            raise TypeError("fusion: unknown option(s) %s (known: %s)" % (sorted(set(fusion) - set(_FUSION_OPTIONS)), ", ".join(_FUSION_OPTIONS)))
+        if fusion is not None and self.regions is None:
+            raise ValueError("fusion= needs a session built with regions= (the panes it completes are the glass regions)")
+        self.fusion = None if fusion is None else ops.check_fusion_options(
+            **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(fusion if isinstance(fusion, dict) else {})))
         self._cache = graphs.GraphCache()                  # every signature is captured at its first sight
         self._graphs = self._cache.entries                 # signature -> {"graph": chain of one, or None, ...}, least recently used first
         self._side = graphs.GraphSide()
@@ -313,7 +332,30 @@ class InferenceSession:
             frame = frame.pin_memory()
         return frame.to(device, non_blocking=True)
 
-    def predict_frames(self, frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False, intrinsics=None):
+    @staticmethod
+    def _sensor_plane(sensor_depth, frame_sizes, device):
+        """sensor_depth -> one zeroed (B, Fh, Fw) uint16 plane on the device with every frame's readings top-left, as the dense
+        results lie.  Host planes go through pinned memory; nothing waits for the device."""
+        B = len(frame_sizes)
+        Fh, Fw = max(s[0] for s in frame_sizes), max(s[1] for s in frame_sizes)
+        if torch.is_tensor(sensor_depth):
+            if sensor_depth.dtype != torch.uint16 or tuple(sensor_depth.shape) != (B, Fh, Fw):
+                raise ValueError("predict_frames: sensor_depth as one tensor must be uint16 %s, got %s %s"
+                                 % ((B, Fh, Fw), sensor_depth.dtype, tuple(sensor_depth.shape)))
+            return InferenceSession._upload_frame(sensor_depth, device).contiguous()
+        if not isinstance(sensor_depth, (list, tuple)) or len(sensor_depth) != B:
+            raise ValueError("predict_frames: sensor_depth is a list of %d uint16 (h, w) tensors or one (B, Fh, Fw) tensor" % B)
+        for k, (t, (h, w)) in enumerate(zip(sensor_depth, frame_sizes)):
+            if not torch.is_tensor(t) or t.dtype != torch.uint16 or tuple(t.shape) != (h, w):
+                raise ValueError("predict_frames: sensor_depth[%d] must be a uint16 (%d, %d) tensor like frame %d, got %s"
+                                 % (k, h, w, k, "%s %s" % (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+        plane = torch.zeros((B, Fh, Fw), dtype=torch.uint16, device=device)
+        for k, (t, (h, w)) in enumerate(zip(sensor_depth, frame_sizes)):
+            plane[k, :h, :w].copy_(InferenceSession._upload_frame(t, device), non_blocking=True)
+        return plane
+
+    def predict_frames(self, frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False, intrinsics=None,
+                       sensor_depth=None):
         """Decoded camera frames in, results at each frame's own size out.  frames: list of uint8 (h,w,3) tensors, host or device,
         of any sizes: at most hip.AUGMENT_BATCH (16) per call, half that with ensemble=True (the forward batch is 2B); no side
         above 16384.  The reference's evaluation transform (RandomResize([size], max_size), ToTensor, Normalize:
@@ -331,6 +373,10 @@ class InferenceSession:
         A session with line_profiles= adds PROFILE_KEYS (LINE PROFILES above); intrinsics: (B,4) (fx, fy, cx, cy) per frame at frame
         size (a tensor or nested sequence) adds line_points - a session without line_profiles raises.
 
+        A session with fusion= and sensor_depth - a list of B uint16 (h, w) tensors at each frame's own size, host or device, or one
+        (B, Fh, Fw) uint16 tensor, millimetres, 0 = no reading - adds FUSION_KEYS (SENSOR FUSION above); sensor_depth without
+        fusion= raises, a plane of another size than its frame raises and names the frame.
+
         -> RESULT_KEYS + "net_sizes": depth / depth_mm / labels (B, Fh, Fw) with (Fh, Fw) the largest frame of the call (outside
         a frame 0 / 0 / 255), sizes (B,2) the FRAME sizes, net_sizes (B,2) the un-padded network sizes, scores / lines / order /
         count as predict() gives them for the B frames, lines in frame pixels.  The dense results, sizes and net_sizes are fresh
@@ -343,6 +389,8 @@ class InferenceSession:
             if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or 0 in f.shape:
                 raise ValueError("predict_frames: frames are uint8 (h, w, 3) tensors")
         dev = self._device()
+        if sensor_depth is not None and self.fusion is None:
+            raise ValueError("predict_frames: sensor_depth needs a session built with fusion=")
         if intrinsics is not None:
             if self.line_profiles is None:
                 raise ValueError("predict_frames: intrinsics need a session built with line_profiles=")
@@ -355,6 +403,7 @@ class InferenceSession:
         net_sizes = [data.resized_shape(w, h, size, max_size) for h, w in frame_sizes]
         if max(max(s) for s in frame_sizes + net_sizes) > 16384:
             raise ValueError("predict_frames: frame and network sizes are limited to 16384 per side")
+        sensor = None if sensor_depth is None else self._sensor_plane(sensor_depth, frame_sizes, dev)
         on_dev = [self._upload_frame(f, dev) for f in frames]
         params = [aug.params(w, h) for h, w in frame_sizes]
         if ensemble:                                       # the flip rides in the resize's read; collated behind the originals
@@ -371,6 +420,10 @@ class InferenceSession:
                 raw["pred_depth"][-1], raw["pred_seg"], nsz, fsz, (max(s[0] for s in frame_sizes), max(s[1] for s in frame_sizes)),
                 self.min_depth, self.max_depth, twin=B if ensemble else 0)
             regions = None if self.regions is None else ops.glass_regions(labels, mm, fsz, depth=depth, **self.regions)
+            fused = None
+            if sensor is not None:
+                fused = ops.sensor_fusion(sensor, labels, depth, mm, fsz, regions["region_map"], regions["region_count"],
+                                          regions["regions"], **self.fusion)
             profiles = None
             if self.line_profiles is not None:             # the rows: the NMS survivors, or the lines above score_thresh through `order`
                 nms = self.line_nms is not None
@@ -383,6 +436,8 @@ class InferenceSession:
             res.update(regions)
         if profiles is not None:
             res.update(profiles)
+        if fused is not None:
+            res.update(fused)
         for k in ("scores", "lines", "order", "count") + (NMS_KEYS if self.line_nms is not None else ()):
             res[k] = post[k][:B].clone() if copy else post[k][:B]
         return res

@@ -2150,6 +2150,109 @@ def glass_regions(labels, depth_mm, sizes, max_regions=32, min_area=100, connect
     return res
 
 
+FUSION_KEYS = ("depth_fused", "depth_fused_mm", "fused_source", "fusion_ring", "fusion_planes", "fusion_scale")
+FUSION_PLANE_FIELDS = ("alpha1", "beta1", "gamma1", "rms1", "n1", "alpha", "beta", "gamma", "rms", "n_used", "status", "spare")
+FUSION_SCALE_FIELDS = ("scale", "n", "sum_sp", "sum_pp")
+FUSED_SOURCES = {"sensor": hip.FUSED_SENSOR, "plane": hip.FUSED_PLANE, "network": hip.FUSED_NETWORK}
+
+
+def fusion_keys():
+    """The keys sensor_fusion returns."""
+    return FUSION_KEYS
+
+
+def _whole(name, v, what="sensor_fusion"):
+    if isinstance(v, bool) or int(v) != v:
+        raise TypeError("%s: %s must be a whole number, got %r" % (what, name, v))
+    return int(v)
+
+
+def check_fusion_options(ring=6, gap=1, trim=2.5, min_ring=50, max_rms=None, align=True, min_align=1000, min_depth=1e-3, max_depth=10.0):
+    """Host validation of sensor_fusion's options (also what InferenceSession(fusion=...) accepts); -> them as a dict."""
+    ring, gap = _whole("ring", ring), _whole("gap", gap)
+    min_ring, min_align = _whole("min_ring", min_ring), _whole("min_align", min_align)
+    if not isinstance(align, bool):
+        raise TypeError("sensor_fusion: align must be True or False, got %r" % (align,))
+    if not 1 <= ring <= hip.FUSION_MAX_RING:
+        raise ValueError("sensor_fusion: 1 <= ring <= %d, got %r" % (hip.FUSION_MAX_RING, ring))
+    if not 0 <= gap < ring:
+        raise ValueError("sensor_fusion: 0 <= gap <= ring - 1, got gap %r with ring %r" % (gap, ring))
+    if not 0.0 <= float(trim) < float("inf"):
+        raise ValueError("sensor_fusion: trim >= 0 (0 = no second fit), got %r" % (trim,))
+    if not 0 <= min_ring < 1 << 31:
+        raise ValueError("sensor_fusion: min_ring >= 0, got %r" % (min_ring,))
+    if max_rms is not None and not float(max_rms) >= 0.0:
+        raise ValueError("sensor_fusion: max_rms must be None or >= 0 (1 / m), got %r" % (max_rms,))
+    if not 0 <= min_align < 1 << 31:
+        raise ValueError("sensor_fusion: min_align >= 0, got %r" % (min_align,))
+    if not 0.0 < float(min_depth) < float(max_depth):
+        raise ValueError("sensor_fusion: 0 < min_depth < max_depth, got %r, %r" % (min_depth, max_depth))
+    lo, hi = region_mm_range(min_depth, max_depth)
+    if lo > hi:
+        raise ValueError("sensor_fusion: no whole millimetre lies in [%r, %r] metres" % (min_depth, max_depth))
+    return dict(ring=ring, gap=gap, trim=float(trim), min_ring=min_ring, max_rms=None if max_rms is None else float(max_rms),
+                align=align, min_align=min_align, min_depth=float(min_depth), max_depth=float(max_depth))
+
+
+def sensor_fusion(sensor_mm, labels, depth, depth_mm, sizes, region_map, region_count, regions, ring=6, gap=1, trim=2.5, min_ring=50,
+                  max_rms=None, align=True, min_align=1000, min_depth=1e-3, max_depth=10.0):
+    """An RGB-D camera's depth plane, corrected where there is glass, on the device (gwd_fusion_ring / gwd_fusion_planes /
+    gwd_fusion_depth, DESIGN.md section 26).  sensor_mm (B,Fh,Fw) uint16 millimetres, 0 = no reading, registered to the frame;
+    labels uint8, depth float32, depth_mm uint16, sizes (B,2) int32 - what InferenceSession.predict_frames returns - and region_map
+    uint8, region_count (B,) int32, regions (B,R,12) int64 of glass_regions for the same frames.  B <= 16, sides <= 16384.  A value
+    is valid when its millimetres lie in region_mm_range(min_depth, max_depth); a pixel outside its frame never takes part.
+
+    -> dict in FUSION_KEYS order:
+    depth_fused (B,Fh,Fw) float32, depth_fused_mm uint16, fused_source uint8 - per pixel the first that applies: 1 (sensor) not
+    glass and a valid reading: the reading; 2 (plane) a pixel of a kept region whose frame plane has status 0 and
+    alpha x + beta y + gamma > 0: clamp(1 / that, min_depth, max_depth); 3 (network) the rest - glass without a usable plane, holes
+    of the sensor: clamp(depth * scale); outside the frames 0 / 0 / 0.
+    fusion_ring (B,Fh,Fw) uint8: r + 1 on the ring of rank r - not glass, a valid reading, no glass pixel within Chebyshev distance
+    `gap`, a pixel of a kept region within `ring` (the smallest such rank) - else 0.
+    fusion_planes (B,R,12) float64 in FUSION_PLANE_FIELDS order: the least-squares plane in inverse depth 1000 / sensor_mm over a
+    region's ring pixels (glass_regions' method), first over all of them, then - trim > 0 - over those within trim * rms1 of the
+    first; status 0 usable, 1 fewer than 3 or collinear samples (NaN), 2 rejected: n_used < min_ring or rms > max_rms (1 / m).
+    fusion_scale (B,4) float64 in FUSION_SCALE_FIELDS order: scale = sum sensor_mm * depth_mm / sum depth_mm^2 over the n pixels
+    that are not glass, have no glass within `gap` and both values valid (exact integers); 1.0 when n < min_align or align=False.
+    Fresh tensors, no host sync; repeated calls give bit-identical results."""
+    opt = check_fusion_options(ring, gap, trim, min_ring, max_rms, align, min_align, min_depth, max_depth)
+    for name, t, dt in (("sensor_mm", sensor_mm, torch.uint16), ("labels", labels, torch.uint8), ("depth", depth, torch.float32),
+                        ("depth_mm", depth_mm, torch.uint16), ("sizes", sizes, torch.int32), ("region_map", region_map, torch.uint8),
+                        ("region_count", region_count, torch.int32), ("regions", regions, torch.int64)):
+        if not torch.is_tensor(t) or t.dtype != dt:
+            raise TypeError("sensor_fusion: %s must be a %s tensor" % (name, dt))
+    if labels.dim() != 3 or 0 in labels.shape:
+        raise ValueError("sensor_fusion: labels must be (B, Fh, Fw), got %s" % (tuple(labels.shape),))
+    B, Fh, Fw = labels.shape
+    if B > hip.AUGMENT_BATCH or max(Fh, Fw) > 16384:
+        raise ValueError("sensor_fusion: at most %d frames of at most 16384 per side, got %s" % (hip.AUGMENT_BATCH, tuple(labels.shape)))
+    for name, t in (("sensor_mm", sensor_mm), ("depth", depth), ("depth_mm", depth_mm), ("region_map", region_map)):
+        if tuple(t.shape) != (B, Fh, Fw):
+            raise ValueError("sensor_fusion: %s must be %s like labels, got %s" % (name, (B, Fh, Fw), tuple(t.shape)))
+    if tuple(sizes.shape) != (B, 2) or tuple(region_count.shape) != (B,):
+        raise ValueError("sensor_fusion: sizes must be (%d, 2) and region_count (%d,)" % (B, B))
+    if regions.dim() != 3 or regions.shape[0] != B or regions.shape[2] != hip.REGION_RECORD or not 1 <= regions.shape[1] <= hip.REGION_MAX:
+        raise ValueError("sensor_fusion: regions must be (%d, 1..%d, %d), got %s" % (B, hip.REGION_MAX, hip.REGION_RECORD, tuple(regions.shape)))
+    lib, dev, R = _lib(), labels.device, regions.shape[1]
+    sensor_mm, labels, depth, depth_mm, sizes, region_map, region_count, regions = (
+        t.contiguous() for t in (sensor_mm, labels, depth, depth_mm, sizes, region_map, region_count, regions))
+    lo, hi = region_mm_range(opt["min_depth"], opt["max_depth"])
+    ws = torch.empty(lib.workspace_bytes(hip.WS_FUSION, B, Fh, Fw), dtype=torch.uint8, device=dev)
+    res = {"depth_fused": torch.empty((B, Fh, Fw), dtype=torch.float32, device=dev),
+           "depth_fused_mm": torch.empty((B, Fh, Fw), dtype=torch.uint16, device=dev),
+           "fused_source": torch.empty((B, Fh, Fw), dtype=torch.uint8, device=dev),
+           "fusion_ring": torch.empty((B, Fh, Fw), dtype=torch.uint8, device=dev),
+           "fusion_planes": torch.empty((B, R, hip.FUSION_PLANE), dtype=torch.float64, device=dev),
+           "fusion_scale": torch.empty((B, 4), dtype=torch.float64, device=dev)}
+    lib.fusion_ring(labels, sensor_mm, depth_mm, sizes, region_map, region_count, R, opt["ring"], opt["gap"], lo, hi, opt["align"],
+                    opt["min_align"], ws, res["fusion_ring"], res["fusion_scale"])
+    lib.fusion_planes(res["fusion_ring"], sensor_mm, sizes, region_count, regions, opt["ring"], lo, hi, opt["trim"], opt["min_ring"],
+                      opt["max_rms"], ws, res["fusion_planes"])
+    lib.fusion_depth(labels, sensor_mm, depth, sizes, region_map, region_count, res["fusion_planes"], res["fusion_scale"], lo, hi,
+                     opt["min_depth"], opt["max_depth"], res["depth_fused"], res["depth_fused_mm"], res["fused_source"])
+    return res
+
+
 PROFILE_KEYS = ("profile_counts", "profile_fits", "profile_kind", "line_points")
 PROFILE_COUNT_FIELDS = ("samples", "on_in", "on_glass", "on_depth", "a_in", "a_glass", "a_depth", "b_in", "b_glass", "b_depth",
                         "region_a", "region_b")

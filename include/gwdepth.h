@@ -89,8 +89,10 @@ const char *gwd_arch(void);
  *   GWD_WS_PLANE           dims = {P, H*W}         -> `workspace` of gwd_plane_loss_forward
  *   GWD_WS_HEALTH          dims = {n_chunks}       -> `partial` of gwd_segment_stats
  *   GWD_WS_REGIONS         dims = {B, Fh, Fw, max_candidates} -> `workspace` of gwd_glass_regions / gwd_region_planes
+ *   GWD_WS_FUSION          dims = {B, Fh, Fw}      -> `workspace` of gwd_fusion_ring / gwd_fusion_planes
  * Returns -1 for an unknown op or a wrong dimension count.                                                     */
-enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3, GWD_WS_HEALTH = 4, GWD_WS_REGIONS = 5 };
+enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3, GWD_WS_HEALTH = 4, GWD_WS_REGIONS = 5,
+       GWD_WS_FUSION = 6 };
 int64_t gwd_query_workspace(int32_t op, const int64_t *dims, int32_t ndims);
 
 /* Implicit-GEMM convolution on MFMA with fused epilogue y = act(scale*conv(x,w) + shift + residual).
@@ -1000,6 +1002,58 @@ int gwd_line_profiles(const void *lines, int32_t lines_dtype, const int32_t *cou
                       int32_t B, int32_t C, int32_t Fh, int32_t Fw, double offset, int32_t max_samples, int32_t lo_mm,
                       int32_t hi_mm, int32_t hi, int32_t lo, int32_t *counts, double *fits, int32_t *kind, double *line_points,
                       void *stream);
+
+/* Sensor depth fusion (csrc/fusion.hip, the fit is csrc/planefit.h): the depth plane of an RGB-D camera,
+ * completed behind glass.  It stands where the reference builds its ground truth - depth_interpolation/depth_interpolation.py:
+ * region_depth_completion fits every labelled pane from the depth measured on its frame, fuse_region_depth writes the pane's depth
+ * over the sensor's - and where a user of predict_frames would today copy three planes to the host and run scipy.ndimage filters and
+ * numpy.linalg.lstsq per frame.  sensor_mm [B][Fh][Fw] uint16 millimetres, 0 = no reading, registered to the frame; labels, depth
+ * (fp32), depth_mm, sizes of predict_frames; region_map, region_count, records of gwd_glass_regions for the same frames.  A value
+ * is VALID when lo_mm <= mm <= hi_mm.  B <= 16, Fh, Fw <= 16384.  A pixel outside its frame never takes part, neither as a sample
+ * nor as a neighbour, whatever byte it holds.  No host synchronisation, no memset, no floating-point atomics, no loop that waits
+ * for another thread; bit-identical from call to call.  workspace: gwd_query_workspace(GWD_WS_FUSION, {B, Fh, Fw}) bytes, 16-byte
+ * aligned, needs no initialisation; the three calls are ordered on one stream and gwd_fusion_planes takes the workspace of the
+ * gwd_fusion_ring call whose ring it reads.
+ *
+ * gwd_fusion_ring: fusion_ring [B][Fh][Fw] uint8, 0 = none, r + 1 = rank r: a pixel inside its frame with labels != 1, a valid
+ *   sensor reading, no pixel with labels == 1 within Chebyshev distance gap and a pixel of a kept region within Chebyshev distance
+ *   ring (1 <= ring <= GWD_FUSION_MAX_RING, 0 <= gap < ring) gets the smallest rank among those regions.  Two separable passes: a
+ *   row pass into the workspace, a column pass over that.
+ *   fusion_scale [B][4] fp64: s, n, sum sensor_mm * depth_mm, sum depth_mm^2 over the n pixels inside the frame that are not glass,
+ *   have no glass within gap and both values valid (exact integers below 2^64, added with integer atomics);
+ *   s = (double)sum_sp / (double)sum_pp, or 1.0 when align == 0, n < min_align or sum_pp == 0.
+ * gwd_fusion_planes: per kept region the plane w = alpha x + beta y + gamma in inverse depth w = 1000 / sensor_mm over its ring
+ *   pixels, by gwd_region_planes' method with coordinates relative to (max(x0 - ring, 0), max(y0 - ring, 0)).  With trim > 0, a
+ *   first fit of status 0 and rms1 > 0, a second fit over the samples with e * e <= (trim * rms1)^2, e = w - ((alpha1 x + beta1 y)
+ *   + gamma1) in fp64 without contraction against the STORED first coefficients; its rms over those samples; otherwise the first
+ *   fit stands.  fusion_planes [B][max_regions][GWD_FUSION_PLANE] fp64: alpha1, beta1, gamma1, rms1, n1, alpha, beta, gamma, rms,
+ *   n_used, status, 0.  status 0 usable; 1 fewer than 3 or collinear samples in either fit (its coefficients and rms NaN); 2 fitted
+ *   but n_used < min_ring or rms > max_rms (pass infinity for no limit).  Rows from region_count on are 0.
+ * gwd_fusion_depth: depth_fused fp32, depth_fused_mm uint16, fused_source uint8 [B][Fh][Fw]; per pixel inside its frame the
+ *   first that applies: GWD_FUSED_SENSOR - labels != 1 and a valid reading: the millimetres copied, fp32 = mm / 1000 as
+ *   gwd_depth_planar forms it; GWD_FUSED_PLANE - region_map names a kept region of status 0 with den = (alpha x + beta y) + gamma
+ *   > 0: clamp(1 / den, min_depth, max_depth) in fp64, rounded once to fp32, millimetres by gwd_dense_postprocess's conversion;
+ *   GWD_FUSED_NETWORK - everything else: clamp((double)depth * s, min_depth, max_depth), rounded and converted alike.  Outside
+ *   the frame 0 / 0 / 0.  Rows of Fw % 4 == 0 in 16-byte aligned planes move four pixels per thread.
+ * -1 on a null pointer or a size / count / range outside its limits, -2 on ring, gap, trim or max_rms outside theirs, -3 when a
+ * pointer is not aligned to its element (the workspace: 16 bytes); nothing is launched then.                                  */
+#define GWD_FUSION_MAX_RING 32
+#define GWD_FUSION_PLANE 12
+#define GWD_FUSED_SENSOR 1
+#define GWD_FUSED_PLANE 2
+#define GWD_FUSED_NETWORK 3
+int gwd_fusion_ring(const uint8_t *labels, const uint16_t *sensor_mm, const uint16_t *depth_mm, const int32_t *sizes,
+                    const uint8_t *region_map, const int32_t *region_count, int32_t B, int32_t Fh, int32_t Fw, int32_t max_regions,
+                    int32_t ring, int32_t gap, int32_t lo_mm, int32_t hi_mm, int32_t align, int32_t min_align, void *workspace,
+                    uint8_t *fusion_ring, double *fusion_scale, void *stream);
+int gwd_fusion_planes(const uint8_t *fusion_ring, const uint16_t *sensor_mm, const int32_t *sizes, const int32_t *region_count,
+                      const int64_t *records, int32_t B, int32_t Fh, int32_t Fw, int32_t max_regions, int32_t ring, int32_t lo_mm,
+                      int32_t hi_mm, double trim, int32_t min_ring, double max_rms, void *workspace, double *fusion_planes,
+                      void *stream);
+int gwd_fusion_depth(const uint8_t *labels, const uint16_t *sensor_mm, const float *depth, const int32_t *sizes,
+                     const uint8_t *region_map, const int32_t *region_count, const double *fusion_planes, const double *fusion_scale,
+                     int32_t B, int32_t Fh, int32_t Fw, int32_t max_regions, int32_t lo_mm, int32_t hi_mm, float min_depth,
+                     float max_depth, float *depth_fused, uint16_t *depth_fused_mm, uint8_t *fused_source, void *stream);
 
 #ifdef __cplusplus
 }
