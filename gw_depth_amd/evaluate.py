@@ -370,7 +370,7 @@ class FrameMetrics:
 
 @torch.no_grad()
 def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size=1024, max_size=1024, pad_to=None, depth_bins=None,
-                    metrics=None, planar=False, sensor=None, fused=False):
+                    metrics=None, planar=False, sensor=None, fused=False, save_dir=None):
     """Scores the samples `indices` (default: all) of a dataset.FrameStore / StreamSource through session.predict_frames at the
     frames' own resolution: `batch` frames per call (at most 16, 8 with ensemble=True), one gwd_eval_frames launch behind each,
     no host sync before the closing copy.  A device-resident FrameStore hands its 16-bit depth planes over in place (record_gt).
@@ -380,6 +380,11 @@ def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size
     fused=True (a session built with fusion=) with sensor=callable: sensor(indices) returns the RGB-D camera's depth planes of those
     samples as predict_frames(sensor_depth=) takes them, and the metrics are fed depth_fused - the sensor's depth completed behind
     glass - in place of depth.
+    save_dir=path: per sample the panels the reference's save_dense_pred and vis_pred_lines show, drawn on the device by ONE
+    gwd_render_frames launch per batch (ops.render_frames; the session needs no render=) and written as PNGs by render.save_panels:
+    <name>.png (the frame), <name>_depth.png, <name>_seg.png (the prediction: the depth that was scored, the labels),
+    <name>_gt-depth.png, <name>_gt-seg.png (the ground truth, read where record_gt / the source left it) and <name>_lines.png (the
+    frame with the glass tinted, the regions outlined and the detected lines).  The metrics are the same bit for bit.
     -> metrics.compute() plus "names": {sample index: name} for FrameMetrics.worst.  Pass `metrics` to keep the accumulator."""
     if planar and not (getattr(session, "regions", None) or {}).get("planar"):
         raise ValueError("evaluate_frames(planar=True) needs an InferenceSession built with regions= (and planar=True in it)")
@@ -404,6 +409,8 @@ def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size
         else:
             frames = source.frames(idx)
             rgb, gt = [f[0] for f in frames], [(f[1], f[2]) for f in frames]
+        if save_dir is not None:                               # the frames go up once: predict_frames uses a device frame where it is
+            rgb = [session._upload_frame(f, session._device()) for f in rgb]
         if fused:
             res = session.predict_frames(rgb, size=size, max_size=max_size, ensemble=ensemble, pad_to=pad_to, sensor_depth=sensor(idx))
             res = dict(res, depth=res["depth_fused"])
@@ -412,9 +419,37 @@ def evaluate_frames(session, source, indices=None, batch=8, ensemble=False, size
         if planar:
             res = dict(res, depth=res["depth_planar"])
         metrics.update(res, gt, ids=idx)
+        if save_dir is not None:
+            _save_frames(session, res, rgb, gt, [source.name(i) for i in idx], save_dir,
+                         "depth_fused_mm" if fused else "depth_planar_mm" if planar else "depth_mm")
     out = metrics.compute()
     out["names"] = {i: source.name(i) for i in indices}
     return out
+
+
+SAVE_SUFFIXES = ("", "_depth", "_seg", "_gt-depth", "_gt-seg", "_lines")      # the reference's five files and the lines
+
+
+def _save_frames(session, res, rgb, gt, names, save_dir, depth_key):
+    """Six panels per frame of one predict_frames call, one launch, one copy to the host, PNGs from a thread pool."""
+    import os
+
+    from . import ops, render
+    dev = res["labels"].device
+    B = len(rgb)
+    gt_mm = [d if d.dtype == torch.uint16 else d.clamp(0, 65535).to(torch.uint16) for d in (g[0].to(dev) for g in gt)]
+    gt_lab = [g[1].to(dev) if g[1].dtype == torch.uint8 else g[1].to(dev).clamp(0, 255).to(torch.uint8) for g in gt]
+    nms = getattr(session, "line_nms", None) is not None
+    kinds = res.get("profile_kind")
+    overlay = {"base": "frame", "tint": 0, "outlines": "region_map" in res, "lines": "kind" if kinds is not None else "score"}
+    panels = ["frame", ("depth", 0), ("labels", 0), ("depth", 1), ("labels", 1), overlay]
+    canvas = ops.render_frames(res["sizes"], panels, frames=rgb, planes=[res[depth_key], gt_mm], label_planes=[res["labels"], gt_lab],
+                               region_map=res.get("region_map"), lines=res["nms_lines" if nms else "lines"],
+                               count=res["nms_count" if nms else "count"], order=None if nms else res["order"],
+                               scores=res["nms_scores" if nms else "scores"], kinds=kinds, canvas_size=tuple(res["labels"].shape[1:]))
+    os.makedirs(save_dir, exist_ok=True)
+    paths = [os.path.join(save_dir, str(n).replace(os.sep, "_") + ".png") for n in names]
+    return render.save_panels(canvas, [(int(f.shape[0]), int(f.shape[1])) for f in rgb], paths, layout="files", suffixes=SAVE_SUFFIXES)
 
 
 def close_line_scores(sorted_flags, n_gt):

@@ -46,6 +46,7 @@ ENTRY_POINTS = [
     "gwd_glass_regions", "gwd_region_planes", "gwd_depth_planar",
     "gwd_line_profiles",
     "gwd_fusion_ring", "gwd_fusion_planes", "gwd_fusion_depth",
+    "gwd_render_frames",
 ]
 
 
@@ -138,8 +139,32 @@ FUSED_SENSOR, FUSED_PLANE, FUSED_NETWORK = 1, 2, 3        # GWD_FUSED_*: fused_s
 PROFILE_MAX_LINES = 2048      # GWD_PROFILE_MAX_LINES: rows per image of gwd_line_profiles
 PROFILE_MAX_SAMPLES = 2048    # GWD_PROFILE_MAX_SAMPLES: samples per line, at most
 PROFILE_COUNTS = 12           # GWD_PROFILE_COUNTS: int32 fields of a line's counts
+RENDER_MAX_PANELS, RENDER_MAX_PLANES, RENDER_MAX_TABLES = 8, 4, 16      # GWD_RENDER_MAX_*: panels, planes of a kind, colour tables per call
+RENDER_MAX_WIDTH8, RENDER_MAX_END_RADIUS = 128, 64    # GWD_RENDER_MAX_WIDTH8 (1/16 pixel), GWD_RENDER_MAX_END_RADIUS (pixels)
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
 COLOR_ADJUST, COLOR_SUMS = 0, 1
+
+
+class RenderSlot(ctypes.Structure):
+    """gwd_render_slot (include/gwdepth.h): one operand, frame by frame."""
+    _fields_ = [("ptr", ctypes.c_void_p * 16), ("pitch", ctypes.c_int32 * 16)]
+
+
+class RenderPanel(ctypes.Structure):
+    """gwd_render_panel (include/gwdepth.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("base", "plane", "table", "lo_mm", "hi_mm", "tint", "tint_alpha", "outlines", "region_table",
+                                              "lines", "line_table", "ends")] + \
+               [(n, ctypes.c_uint8 * 4) for n in ("void_rgb", "tint_rgb", "line_rgb", "end_rgb")]
+
+
+class RenderDesc(ctypes.Structure):
+    """gwd_render_desc (include/gwdepth.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("canvas", "sizes", "tables", "lines", "count", "order", "scores", "kinds")] + \
+               [(n, ctypes.c_double) for n in ("min_score", "score_lo", "score_k")] + \
+               [(n, ctypes.c_int32) for n in ("B", "P", "Fh", "Fw", "C", "n_planes", "n_label_planes", "n_tables", "lines_dtype",
+                                              "scores_dtype", "width8", "end_radius", "has_frames", "has_region_map")] + \
+               [("ext_h", ctypes.c_int32 * 16), ("ext_w", ctypes.c_int32 * 16), ("frames", RenderSlot), ("region_map", RenderSlot),
+                ("planes", RenderSlot * 4), ("label_planes", RenderSlot * 4), ("panels", RenderPanel * 8)]
 
 
 class ResampleJob(ctypes.Structure):
@@ -329,6 +354,7 @@ class HipLibrary:
         L.gwd_fusion_ring.argtypes = [vp] * 6 + [i32] * 10 + [vp] * 4
         L.gwd_fusion_planes.argtypes = [vp] * 5 + [i32] * 7 + [ctypes.c_double, i32, ctypes.c_double] + [vp] * 3
         L.gwd_fusion_depth.argtypes = [vp] * 8 + [i32] * 6 + [f32, f32] + [vp] * 4
+        L.gwd_render_frames.argtypes = [ctypes.POINTER(RenderDesc), vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1417,6 +1443,80 @@ class HipLibrary:
             _ptr(counts), _ptr(fits), _ptr(kind), _ptr(line_points),
             self._stream(lines, count, order, labels, depth_mm, sizes, region_map, intrinsics, counts, fits, kind, line_points)),
             "gwd_line_profiles")
+
+    @staticmethod
+    def render_desc(canvas, sizes, tables, panels, frames, planes, label_planes, region_map, lines, count, order, scores, kinds, opts):
+        """The gwd_render_desc of a call (no device work): every operand per frame, with its row pitch; ext = what the operands of a
+        frame cover.  Raises on a dtype, a layout or a size the kernel does not take."""
+        HipLibrary._typed("gwd_render_frames", ((canvas, torch.uint8), (sizes, torch.int32), (tables, torch.uint8), (count, torch.int32),
+                                                (order, torch.int32), (kinds, torch.int32)))
+        if canvas.dim() != 5 or canvas.shape[4] != 3 or not canvas.is_contiguous():
+            raise ValueError("gwd_render_frames: canvas must be a contiguous (B, P, Fh, Fw, 3) tensor")
+        B, P, Fh, Fw = canvas.shape[:4]
+        if not 1 <= B <= 16 or P != len(panels) or not 1 <= P <= RENDER_MAX_PANELS or tuple(sizes.shape) != (B, 2) or tables.dim() != 3 \
+                or tuple(tables.shape[1:]) != (256, 3) or not 1 <= tables.shape[0] <= RENDER_MAX_TABLES or len(planes) > RENDER_MAX_PLANES \
+                or len(label_planes) > RENDER_MAX_PLANES:
+            raise ValueError("gwd_render_frames: operand sizes do not match (B, P, Fh, Fw) = (%d, %d, %d, %d)" % (B, P, Fh, Fw))
+        d = RenderDesc()
+        d.canvas, d.sizes, d.tables = canvas.data_ptr(), _ptr(sizes).value, _ptr(tables).value
+        d.B, d.P, d.Fh, d.Fw, d.n_planes, d.n_label_planes, d.n_tables = B, P, Fh, Fw, len(planes), len(label_planes), tables.shape[0]
+        ext = [[Fh, Fw] for _ in range(B)]
+
+        def fill(slot, views, dtype, what, channels=None):
+            if len(views) != B:
+                raise ValueError("gwd_render_frames: %s must hold one view per frame (%d), got %d" % (what, B, len(views)))
+            for b, t in enumerate(views):
+                ok = t.dtype == dtype and t.dim() == (2 if channels is None else 3) and 0 not in t.shape and t.stride(0) < 2 ** 31
+                ok = ok and (t.stride(1) == 1 if channels is None else (t.shape[2] == channels and t.stride(2) == 1 and t.stride(1) == channels))
+                if not ok or (t.shape[0] > 1 and t.stride(0) < t.shape[1] * (channels or 1)):
+                    raise ValueError("gwd_render_frames: %s[%d] must be a %s %s view with dense rows, got %s %s strides %s"
+                                     % (what, b, dtype, "(h, w)" if channels is None else "(h, w, %d)" % channels, t.dtype, tuple(t.shape), t.stride()))
+                slot.ptr[b], slot.pitch[b] = t.data_ptr(), max(t.stride(0), 1)
+                ext[b] = [min(ext[b][0], t.shape[0]), min(ext[b][1], t.shape[1])]
+
+        if frames is not None:
+            fill(d.frames, frames, torch.uint8, "frames", 3)
+            d.has_frames = 1
+        if region_map is not None:
+            fill(d.region_map, region_map, torch.uint8, "region_map")
+            d.has_region_map = 1
+        for i, views in enumerate(planes):
+            fill(d.planes[i], views, torch.uint16, "planes[%d]" % i)
+        for i, views in enumerate(label_planes):
+            fill(d.label_planes[i], views, torch.uint8, "label_planes[%d]" % i)
+        for b in range(B):
+            d.ext_h[b], d.ext_w[b] = ext[b]
+        for k, r in enumerate(panels):
+            pn = d.panels[k]
+            for n in ("base", "plane", "table", "lo_mm", "hi_mm", "tint", "tint_alpha", "outlines", "region_table", "lines", "line_table", "ends"):
+                setattr(pn, n, int(r[n]))
+            for n, key in (("void_rgb", "void"), ("tint_rgb", "tint_rgb"), ("line_rgb", "line_rgb"), ("end_rgb", "end_rgb")):
+                getattr(pn, n)[:3] = [int(v) for v in r[key]]
+        if lines is not None:
+            if lines.dtype not in (torch.float32, torch.float64) or (scores is not None and scores.dtype not in (torch.float32, torch.float64)):
+                raise TypeError("gwd_render_frames: lines and scores must be float32 or float64")
+            C = lines.shape[1] if lines.dim() == 3 else -1
+            if tuple(lines.shape) != (B, C, 4) or not 1 <= C <= PROFILE_MAX_LINES or count is None or count.numel() != B \
+                    or any(t is not None and tuple(t.shape) != (B, C) for t in (order, scores, kinds)):
+                raise ValueError("gwd_render_frames: line operands do not match (B, C) = (%d, %d)" % (B, C))
+            d.lines, d.count, d.order, d.scores, d.kinds = (None if t is None else _ptr(t).value for t in (lines, count, order, scores, kinds))
+            d.C, d.lines_dtype = C, 1 if lines.dtype == torch.float64 else 0
+            d.scores_dtype = 1 if scores is not None and scores.dtype == torch.float64 else 0
+        elif any(t is not None for t in (count, order, scores, kinds)):
+            raise ValueError("gwd_render_frames: count, order, scores and kinds belong to lines")
+        d.width8, d.end_radius = int(opts["width8"]), int(opts["end_radius"])
+        d.min_score, d.score_lo, d.score_k = float(opts["min_score"]), float(opts["score_lo"]), float(opts["score_k"])
+        return d
+
+    def render_frames(self, canvas, sizes, tables, panels, frames, planes, label_planes, region_map, lines, count, order, scores, kinds, opts):
+        """gwd_render_frames: canvas (B,P,Fh,Fw,3) uint8 out, every byte written.  sizes (B,2) int32, tables (T,256,3) uint8, panels:
+        the records of render.resolve; frames: None or B uint8 (h,w,3) views; planes / label_planes: lists of B-lists of uint16 / uint8
+        (h,w) views with unit column stride (any row pitch); region_map: None or a B-list; lines (B,C,4) float32 / float64 with count
+        (B,), order / scores / kinds (B,C) or None; opts: width8, end_radius, min_score, score_lo, score_k."""
+        d = self.render_desc(canvas, sizes, tables, panels, frames, planes, label_planes, region_map, lines, count, order, scores, kinds, opts)
+        every = [canvas, sizes, tables, lines, count, order, scores, kinds] + list(frames or []) + list(region_map or []) + \
+            [t for views in list(planes) + list(label_planes) for t in views]
+        self._check(self.lib.gwd_render_frames(ctypes.byref(d), self._stream(*every)), "gwd_render_frames")
 
 
 _LIB = None

@@ -28,6 +28,8 @@ _PROFILE_OPTIONS = ("offset", "max_samples", "min_depth", "max_depth", "hi", "lo
 PROFILE_KEYS = ops.PROFILE_KEYS                                        # ... with line_profiles= (line_points only when intrinsics are passed)
 _FUSION_OPTIONS = ("ring", "gap", "trim", "min_ring", "max_rms", "align", "min_align", "min_depth", "max_depth")
 FUSION_KEYS = ops.FUSION_KEYS                                          # ... with fusion=, by a call that passes sensor_depth=
+_RENDER_OPTIONS = ("panels", "width", "end_radius", "min_score", "score_range")
+RENDER_KEYS = ops.RENDER_KEYS                                          # ... with render=
 
 
 class InferenceSession:
@@ -88,11 +90,23 @@ class InferenceSession:
     stream, as fresh tensors, with no host sync.  A call without sensor_depth returns what it returns today.  predict() does not
     take part.
 
+    RENDER.  render=None (the default): nothing is allocated, predict_frames issues the launches and returns the keys it always did.
+    render=True or a dict (panels, and ops.render_frames' options width, end_radius, min_score, score_range): predict_frames also
+    returns RENDER_KEYS - canvas (B, P, Fh, Fw, 3) uint8, RGB panels of the call's own frames and results at frame size, drawn by ONE
+    launch (gwd_render_frames) behind everything else on the session's stream, a fresh tensor, no host sync; render.save_panels
+    writes it out.  The default panels: the frame with the glass tinted, the regions outlined (with regions=) and the lines on top -
+    the NMS survivors with line_nms, else the lines above score_thresh through `order`; coloured by profile_kind with
+    line_profiles=, else by score; the depth (depth_fused_mm when the call fused, else depth_mm); the labels.  Panels of one's own
+    are ops.render_frames' with the planes named: base ("depth", "depth_mm" | "depth_planar_mm" | "depth_fused_mm" | "depth" = the
+    default choice) or ("labels", "labels" | "region_map" | "fused_source" | "fusion_ring"), tint: such a uint8 name.  A panel that
+    names a plane the session does not produce raises here.  predict() does not take part.
+
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
 
     def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6,
-                 line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None, line_profiles=None, fusion=None):
+                 line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None, line_profiles=None, fusion=None,
+                 render=None):
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
         if line_nms_order not in ("score", "query"):
@@ -127,6 +141,7 @@ class InferenceSession:
             raise ValueError("fusion= needs a session built with regions= (the panes it completes are the glass regions)")
         self.fusion = None if fusion is None else ops.check_fusion_options(
             **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(fusion if isinstance(fusion, dict) else {})))
+        self.render = self._check_render(render)
         self._cache = graphs.GraphCache()                  # every signature is captured at its first sight
         self._graphs = self._cache.entries                 # signature -> {"graph": chain of one, or None, ...}, least recently used first
         self._side = graphs.GraphSide()
@@ -140,6 +155,83 @@ class InferenceSession:
             flat = self._own[1]
             spans.append((flat.data_ptr(), flat.data_ptr() + flat.numel() * flat.element_size()))
         self.weights = ops.WeightCache(spans, frozen=True) if compute_dtype == torch.bfloat16 else None
+
+    # ------------------------------------------------------------------ render=
+    def _check_render(self, render):
+        """render= -> None or dict(panels, options); every panel checked against what this session produces."""
+        from . import render as R
+        if render is None:
+            return None
+        if render is not True and not isinstance(render, dict):
+            raise TypeError("render must be None, True or a dict of panels and ops.render_frames' options, got %r" % (render,))
+        given = render if isinstance(render, dict) else {}
+        if set(given) - set(_RENDER_OPTIONS):
+            raise TypeError("render: unknown option(s) %s (known: %s)" % (sorted(set(given) - set(_RENDER_OPTIONS)), ", ".join(_RENDER_OPTIONS)))
+        R.check_options(**{k: v for k, v in given.items() if k != "panels"})
+        planar = self.regions is not None and "depth_planar_mm" in ops.region_keys(self.regions["planes"], self.regions["planar"])
+        depth_names = ("depth", "depth_mm") + (("depth_planar_mm",) if planar else ()) + (("depth_fused_mm",) if self.fusion is not None else ())
+        label_names = ("labels",) + (("region_map",) if self.regions is not None else ()) + \
+            (("fused_source", "fusion_ring") if self.fusion is not None else ())
+        panels = given.get("panels")
+        if panels is None:
+            panels = [{"base": "frame", "tint": "labels", "outlines": self.regions is not None,
+                       "lines": "kind" if self.line_profiles is not None else "score"},
+                      {"base": ("depth", "depth")}, {"base": ("labels", "labels")}]
+        if isinstance(panels, dict) or not isinstance(panels, (list, tuple)):
+            raise ValueError("render: panels is a list of panels")
+        named = []
+        for k, p in enumerate(panels):
+            p = dict(p) if isinstance(p, dict) else {"base": p}
+            base = p.get("base", "black")
+            if isinstance(base, str) and base in ("depth", "labels"):
+                base = (base, base)
+            if isinstance(base, tuple) and len(base) == 2 and base[0] in ("depth", "labels"):
+                names = depth_names if base[0] == "depth" else label_names
+                if base[1] not in names:
+                    raise ValueError("render: panel %d names the %s plane %r, this session produces %s" % (k, base[0], base[1], ", ".join(names)))
+            if p.get("tint") is not None and p["tint"] not in label_names:
+                raise ValueError("render: panel %d tints by %r, this session produces %s" % (k, p["tint"], ", ".join(label_names)))
+            if p.get("outlines") and self.regions is None:
+                raise ValueError("render: panel %d draws region outlines: that needs a session built with regions=" % k)
+            if p.get("lines") == "kind" and self.line_profiles is None:
+                raise ValueError("render: panel %d colours lines by kind: that needs a session built with line_profiles=" % k)
+            p["base"] = base
+            named.append(p)
+        # the rest of every panel is checked as ops.render_frames will check it (indices stand in for the names)
+        stand_in = lambda p: dict(p, base=(p["base"][0], 0) if isinstance(p["base"], tuple) and len(p["base"]) == 2 else p["base"],
+                                  tint=None if p.get("tint") is None else 0)
+        R.check_panels([stand_in(p) for p in named])
+        return dict(panels=named, options={k: v for k, v in given.items() if k != "panels"})
+
+    def _render(self, frames, res, post, B, fused):
+        """The canvas of one predict_frames call from the tensors it already holds: planes are handed over by name."""
+        nms = self.line_nms is not None
+        planes, label_planes, panels = [], [], []
+
+        def index(names, pool, name):
+            if name == "depth":
+                name = "depth_fused_mm" if fused else "depth_mm"
+            if name not in res:
+                raise ValueError("predict_frames: a render panel names %r, which this call did not produce (sensor_depth=?)" % name)
+            if name not in names:
+                names.append(name)
+                pool.append(res[name])
+            return names.index(name)
+
+        depth_names, label_names = [], []
+        for p in self.render["panels"]:
+            p = dict(p)
+            if isinstance(p["base"], tuple):
+                kind, name = p["base"]
+                p["base"] = (kind, index(depth_names, planes, name) if kind == "depth" else index(label_names, label_planes, name))
+            if p.get("tint") is not None:
+                p["tint"] = index(label_names, label_planes, p["tint"])
+            panels.append(p)
+        return ops.render_frames(res["sizes"], panels, frames=frames, planes=planes, label_planes=label_planes,
+                                 region_map=res.get("region_map"), lines=post["nms_lines" if nms else "lines"][:B],
+                                 count=post["nms_count" if nms else "count"][:B], order=None if nms else post["order"][:B],
+                                 scores=post["nms_scores" if nms else "scores"][:B], kinds=res.get("profile_kind"),
+                                 canvas_size=tuple(res["labels"].shape[1:]), **self.render["options"])
 
     # ------------------------------------------------------------------ the reference passes `model`
     def eval(self):
@@ -377,6 +469,8 @@ class InferenceSession:
         (B, Fh, Fw) uint16 tensor, millimetres, 0 = no reading - adds FUSION_KEYS (SENSOR FUSION above); sensor_depth without
         fusion= raises, a plane of another size than its frame raises and names the frame.
 
+        A session with render= adds RENDER_KEYS (RENDER above).
+
         -> RESULT_KEYS + "net_sizes": depth / depth_mm / labels (B, Fh, Fw) with (Fh, Fw) the largest frame of the call (outside
         a frame 0 / 0 / 255), sizes (B,2) the FRAME sizes, net_sizes (B,2) the un-padded network sizes, scores / lines / order /
         count as predict() gives them for the B frames, lines in frame pixels.  The dense results, sizes and net_sizes are fresh
@@ -438,6 +532,9 @@ class InferenceSession:
             res.update(profiles)
         if fused is not None:
             res.update(fused)
+        if self.render is not None:                        # behind everything else, on the same stream; the uploaded frames are read where they are
+            with torch.no_grad(), self._on_stream():
+                res["canvas"] = self._render(on_dev[:B], res, post, B, fused is not None)
         for k in ("scores", "lines", "order", "count") + (NMS_KEYS if self.line_nms is not None else ()):
             res[k] = post[k][:B].clone() if copy else post[k][:B]
         return res

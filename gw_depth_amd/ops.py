@@ -2332,3 +2332,100 @@ def line_profiles(lines, count, labels, depth_mm, sizes, order=None, region_map=
                          opt["max_samples"], lo_mm, hi_mm, opt["hi"], opt["lo"], res["profile_counts"], res["profile_fits"],
                          res["profile_kind"], res.get("line_points"))
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------- rendering
+RENDER_KEYS = ("canvas",)
+_RENDER_TABLES = {}            # (device, the tables' bytes) -> the tables on the device: the defaults are uploaded once
+
+
+def _render_tables(tables, device):
+    key = (str(device), tables.tobytes())
+    t = _RENDER_TABLES.get(key)
+    if t is None:
+        if len(_RENDER_TABLES) >= 32:
+            _RENDER_TABLES.clear()
+        t = _RENDER_TABLES[key] = torch.from_numpy(tables).to(device)
+    return t
+
+
+def _render_views(value, B, name):
+    """One (B, h, w[, 3]) tensor or B separate views -> a list of B views (no copy)."""
+    if value is None:
+        return None
+    if torch.is_tensor(value):
+        if value.shape[0] != B:
+            raise ValueError("render_frames: %s holds %d frames, sizes %d" % (name, value.shape[0], B))
+        return [value[b] for b in range(B)]
+    if not isinstance(value, (list, tuple)) or len(value) != B or not all(torch.is_tensor(t) for t in value):
+        raise ValueError("render_frames: %s is one tensor or a list of %d tensors" % (name, B))
+    return list(value)
+
+
+def render_frames(sizes, panels, frames=None, planes=None, label_planes=None, region_map=None, lines=None, count=None, order=None,
+                  scores=None, kinds=None, out=None, **options):
+    """uint8 RGB panels of predict_frames' results at frame size, on the device, in ONE launch (gwd_render_frames, DESIGN.md section
+    27).  sizes (B,2) int32 (fh, fw) on the device; panels: 1..8 dicts (render.PANEL_KEYS; a bare base stands for {"base": base}):
+      base           "black", "frame", ("depth", i): planes[i] (uint16 millimetres) through `table` ((256,3) uint8, default
+                     matplotlib's jet) over `range` = (lo_mm, hi_mm) (default 0 .. 8500), 0 mm: `void`; ("labels", i):
+                     label_planes[i] (uint8) through `table` (default the PASCAL-VOC palette, 255 black);
+      tint           the index of a label plane: where it is 1 the pixel moves `tint_alpha` / 256 of the way to `tint_color`;
+      outlines       True: the outline pixels of region_map's regions in `region_colors`;
+      lines          "score" (`score_table` over the call's score_range), "kind" (`kind_colors` by kinds) or an (r, g, b);
+      ends           discs at both ends of every drawn row (default: with lines) in `end_color`.
+    frames: B uint8 (h,w,3) tensors; planes / label_planes: a plane or a list of planes, each ONE (B,h,w) tensor or B separate
+    (h,w) views (unit column stride, any row pitch: nothing is copied); region_map likewise.  lines (B,C,4) float32 / float64
+    frame pixels with count (B,) int32, and order (B,C) int32, scores (B,C) (both indexed as ops.line_profiles takes them: row r
+    reads lines[b, order[b, r]] and that row's score), kinds (B,C) int32 = profile_kind (indexed by the row r itself).
+    options (render.RENDER_OPTIONS): width=2.0 pixels (<= 16), end_radius=2 pixels (0: none), min_score (rows below it, or with a NaN
+    score, are not drawn), score_range=(0.92, 1.02), canvas_size=(Fh, Fw) (default: the largest operand).
+    -> canvas (B, P, Fh, Fw, 3) uint8, a fresh tensor (or `out`, a contiguous uint8 tensor of that shape on the device) every byte
+    of which the launch wrote; a pixel outside its frame is 0.  A frame is clipped to what its operands cover.  No host sync; repeated calls are bit-identical."""
+    from . import render as R
+    if set(options) - set(R.RENDER_OPTIONS):
+        raise TypeError("render_frames: unknown option(s) %s (known: %s)" % (sorted(set(options) - set(R.RENDER_OPTIONS)), ", ".join(R.RENDER_OPTIONS)))
+    opts = R.check_options(**options)
+    if not torch.is_tensor(sizes) or sizes.dtype != torch.int32 or sizes.dim() != 2 or sizes.shape[1] != 2:
+        raise TypeError("render_frames: sizes must be a (B, 2) int32 tensor")
+    B = sizes.shape[0]
+    if not 1 <= B <= hip.AUGMENT_BATCH:
+        raise ValueError("render_frames: 1..%d frames per call, got %d" % (hip.AUGMENT_BATCH, B))
+
+    def plane_list(value, name):
+        if value is None:
+            return []
+        if torch.is_tensor(value) or (isinstance(value, (list, tuple)) and len(value) and torch.is_tensor(value[0]) and value[0].dim() == 2):
+            value = [value]                               # one plane: a (B,h,w) tensor, or B views
+        if len(value) > hip.RENDER_MAX_PLANES:
+            raise ValueError("render_frames: at most %d %s, got %d" % (hip.RENDER_MAX_PLANES, name, len(value)))
+        return [_render_views(v, B, "%s[%d]" % (name, i)) for i, v in enumerate(value)]
+
+    frames = _render_views(frames, B, "frames")
+    if frames is not None:                                # a frame is read where it lies when its pixels are dense, whatever its row pitch
+        frames = [f if f.dim() != 3 or (f.stride(2) == 1 and f.stride(1) == 3) else f.contiguous() for f in frames]
+    region_map = _render_views(region_map, B, "region_map")
+    planes, label_planes = plane_list(planes, "planes"), plane_list(label_planes, "label_planes")
+    for views, dt, name in [(frames, torch.uint8, "frames"), (region_map, torch.uint8, "region_map")] + \
+            [(v, torch.uint16, "planes") for v in planes] + [(v, torch.uint8, "label_planes") for v in label_planes]:
+        if views is not None and any(t.dtype != dt for t in views):
+            raise TypeError("render_frames: %s must be %s" % (name, dt))
+    for t, name, dts in ((lines, "lines", (torch.float32, torch.float64)), (count, "count", (torch.int32,)), (order, "order", (torch.int32,)),
+                         (scores, "scores", (torch.float32, torch.float64)), (kinds, "kinds", (torch.int32,))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype not in dts):
+            raise TypeError("render_frames: %s must be a %s tensor" % (name, " or ".join(str(d) for d in dts)))
+    tables, recs = R.resolve(panels, len(planes), len(label_planes), frames is not None, region_map is not None, lines is not None,
+                             scores is not None, kinds is not None)
+    every = (frames or []) + (region_map or []) + [t for views in planes + label_planes for t in views]
+    Fh, Fw = opts["canvas_size"] or (max([t.shape[0] for t in every] + [1]), max([t.shape[1] for t in every] + [1]))
+    if max(Fh, Fw) > 16384:
+        raise ValueError("render_frames: sides are limited to 16384, got %s" % ((Fh, Fw),))
+    dev = sizes.device
+    c = lambda t: None if t is None else t.contiguous()
+    shape = (B, len(recs), Fh, Fw, 3)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != dev
+                            or not out.is_contiguous()):
+        raise ValueError("render_frames: out must be a contiguous uint8 %s tensor on %s" % (shape, dev))
+    canvas = torch.empty(shape, dtype=torch.uint8, device=dev) if out is None else out
+    _lib().render_frames(canvas, c(sizes), _render_tables(tables, dev), recs, frames, planes, label_planes, region_map, c(lines), c(count),
+                         c(order), c(scores), c(kinds), opts)
+    return canvas

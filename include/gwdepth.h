@@ -1055,6 +1055,82 @@ int gwd_fusion_depth(const uint8_t *labels, const uint16_t *sensor_mm, const flo
                      int32_t B, int32_t Fh, int32_t Fw, int32_t max_regions, int32_t lo_mm, int32_t hi_mm, float min_depth,
                      float max_depth, float *depth_fused, uint16_t *depth_fused_mm, uint8_t *fused_source, void *stream);
 
+/* Rendering of predict_frames' results (csrc/render.hip, the scalar geometry is csrc/rendergeom.h): uint8 RGB
+ * panels at frame size, ONE launch for all P panels of all B frames, integer arithmetic throughout; tests/render_ref.py states the
+ * same in numpy and the kernel equals it bit for bit.  canvas [B][P][Fh][Fw][3] uint8, 16-byte aligned; EVERY byte of it is written
+ * (a pixel outside its frame is 0 0 0): no memset.  sizes [B][2] int32 (fh, fw) on the device; frame b is fh x fw clamped to
+ * 0 .. min(Fh, ext_h[b]) x 0 .. min(Fw, ext_w[b]) - ext: what every operand handed over for frame b covers, so nothing is read
+ * outside an operand whatever sizes holds.  B <= 16, P <= GWD_RENDER_MAX_PANELS, Fh, Fw <= 16384.
+ * Operands travel per frame: a slot holds B pointers and B row pitches (frames: bytes per row, 3 bytes per pixel; planes: elements
+ * per row), so a plane may be one [B][Fh][Fw] tensor or B separate views.  planes: uint16 millimetres; label_planes and region_map:
+ * uint8.  tables [n_tables][256][3] uint8 on the device: every colour table of the call (depth tables, palettes, region colours
+ * indexed by rank, the score table, the 5 colours of profile_kind).
+ * A panel's pixel, layer over layer:
+ *   base     GWD_RENDER_BLACK; GWD_RENDER_FRAME: the frame's RGB; GWD_RENDER_DEPTH: planes[plane] through tables[table] at
+ *            clamp((2 * 255 * (mm - lo_mm) + span) / (2 * span), 0, 255), span = hi_mm - lo_mm >= 1, mm == 0: void_rgb;
+ *            GWD_RENDER_LABELS: label_planes[plane] through tables[table].
+ *   tint     tint >= 0: where label_planes[tint] == 1, c = (c * (256 - tint_alpha) + tint_rgb * tint_alpha + 128) >> 8.
+ *   outline  outlines != 0 (needs region_map): a pixel with rank r = region_map > 0 one of whose 4 neighbours lies outside the
+ *            frame or holds another value takes tables[region_table][r - 1].
+ *   lines    rows r < count[b] (clamped to 0 .. C) of lines [B][C][4] fp32 / fp64 (GWD_LINES_*), through order [B][C] when given
+ *            (src = order[b][r], outside 0 .. C-1: not drawn); not drawn either with a non-finite coordinate or one above 32767 in
+ *            magnitude, or, with scores [B][C] (fp32 / fp64, indexed by src), a score that is NaN or below min_score.  Ends are
+ *            quantised to 1/16 pixel, X = floor(16 x + 0.5); pixel (ix, iy) is the point (16 ix + 8, 16 iy + 8); it is covered when it
+ *            lies within width8 (= round(8 * width in pixels), 1 .. GWD_RENDER_MAX_WIDTH8) of the segment, ties inside, in exact int64
+ *            arithmetic (rendergeom.h: rg_covered).  Where several rows cover a pixel the LOWEST row index wins.  GWD_RENDER_LINES_SCORE:
+ *            tables[line_table] at clamp(floor((score - score_lo) * score_k), 0, 255) in fp64; GWD_RENDER_LINES_KIND:
+ *            tables[line_table][kinds[b][r]] (kinds [B][C] int32 indexed by the ROW, values outside 0 .. 4 count as 0);
+ *            GWD_RENDER_LINES_FIXED: line_rgb.
+ *   ends     ends != 0: discs of end_radius pixels (0 .. GWD_RENDER_MAX_END_RADIUS, 0 = none) about both ends of every drawn row,
+ *            the same integer test, above all lines, end_rgb.
+ * width8 and end_radius hold for the whole call: coverage is decided once per pixel, the panels only choose colours.
+ * One workgroup per 64 x 16 pixel tile of one frame; it bins the rows that can touch its tile into an LDS list in row order
+ * (a conservative integer test), draws and continues when the list is full, and stores every panel's tile through LDS in 16-byte
+ * pieces with a scalar head and tail per row.  No atomics, no workspace, no scratch; repeated calls are bit-identical; a frame's
+ * panels depend on neither its slot nor its neighbours.
+ * -1 on a null pointer or a size / count / range outside its limits, -2 on an enum, an index or a dtype outside its range or a
+ * layer whose operand is missing, -3 when a pointer is not aligned to its element (the canvas: 16 bytes); nothing is launched then. */
+#define GWD_RENDER_MAX_PANELS 8
+#define GWD_RENDER_MAX_PLANES 4
+#define GWD_RENDER_MAX_TABLES 16
+#define GWD_RENDER_MAX_WIDTH8 128
+#define GWD_RENDER_MAX_END_RADIUS 64
+#define GWD_RENDER_BLACK 0
+#define GWD_RENDER_FRAME 1
+#define GWD_RENDER_DEPTH 2
+#define GWD_RENDER_LABELS 3
+#define GWD_RENDER_LINES_NONE 0
+#define GWD_RENDER_LINES_SCORE 1
+#define GWD_RENDER_LINES_KIND 2
+#define GWD_RENDER_LINES_FIXED 3
+typedef struct gwd_render_slot {
+    const void *ptr[16];
+    int32_t pitch[16];
+} gwd_render_slot;
+typedef struct gwd_render_panel {
+    int32_t base, plane, table, lo_mm, hi_mm;
+    int32_t tint, tint_alpha;
+    int32_t outlines, region_table;
+    int32_t lines, line_table, ends;
+    uint8_t void_rgb[4], tint_rgb[4], line_rgb[4], end_rgb[4];       /* r, g, b, unused */
+} gwd_render_panel;
+typedef struct gwd_render_desc {
+    uint8_t *canvas;
+    const int32_t *sizes;
+    const uint8_t *tables;
+    const void *lines;                                    /* NULL: no lines (C = 0) */
+    const int32_t *count, *order;
+    const void *scores;
+    const int32_t *kinds;
+    double min_score, score_lo, score_k;
+    int32_t B, P, Fh, Fw, C, n_planes, n_label_planes, n_tables, lines_dtype, scores_dtype, width8, end_radius, has_frames,
+        has_region_map;
+    int32_t ext_h[16], ext_w[16];
+    gwd_render_slot frames, region_map, planes[GWD_RENDER_MAX_PLANES], label_planes[GWD_RENDER_MAX_PLANES];
+    gwd_render_panel panels[GWD_RENDER_MAX_PANELS];
+} gwd_render_desc;
+int gwd_render_frames(const gwd_render_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
