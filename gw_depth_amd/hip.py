@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GWD_LIB") or os.path.join(_HERE, "libgwdepth_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3, 4
-WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS, WS_FUSION = 0, 1, 2, 3, 4, 5, 6          # gwd_query_workspace ops
+WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS, WS_FUSION, WS_CLOUD = 0, 1, 2, 3, 4, 5, 6, 7          # gwd_query_workspace ops
 GATHER_CONV, GATHER_TRANSPOSED, GATHER_UPSAMPLED = 0, 1, 2
 RESAMPLE_BILINEAR_AC, RESAMPLE_NEAREST = 0, 1
 
@@ -47,6 +47,7 @@ ENTRY_POINTS = [
     "gwd_line_profiles",
     "gwd_fusion_ring", "gwd_fusion_planes", "gwd_fusion_depth",
     "gwd_render_frames",
+    "gwd_point_cloud",
 ]
 
 
@@ -141,6 +142,10 @@ PROFILE_MAX_SAMPLES = 2048    # GWD_PROFILE_MAX_SAMPLES: samples per line, at mo
 PROFILE_COUNTS = 12           # GWD_PROFILE_COUNTS: int32 fields of a line's counts
 RENDER_MAX_PANELS, RENDER_MAX_PLANES, RENDER_MAX_TABLES = 8, 4, 16      # GWD_RENDER_MAX_*: panels, planes of a kind, colour tables per call
 RENDER_MAX_WIDTH8, RENDER_MAX_END_RADIUS = 128, 64    # GWD_RENDER_MAX_WIDTH8 (1/16 pixel), GWD_RENDER_MAX_END_RADIUS (pixels)
+CLOUD_TILE = 1024         # GWD_CLOUD_TILE: candidates of one frame per workgroup of gwd_point_cloud
+CLOUD_RECORD = 32         # GWD_CLOUD_RECORD: bytes of a point
+CLOUD_MAX_STRIDE = 16     # GWD_CLOUD_MAX_STRIDE
+CLOUD_KEEP = {"all": 0, "glass": 1, "non_glass": 2}       # GWD_CLOUD_KEEP_*
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
 COLOR_ADJUST, COLOR_SUMS = 0, 1
 
@@ -165,6 +170,15 @@ class RenderDesc(ctypes.Structure):
                                               "scores_dtype", "width8", "end_radius", "has_frames", "has_region_map")] + \
                [("ext_h", ctypes.c_int32 * 16), ("ext_w", ctypes.c_int32 * 16), ("frames", RenderSlot), ("region_map", RenderSlot),
                 ("planes", RenderSlot * 4), ("label_planes", RenderSlot * 4), ("panels", RenderPanel * 8)]
+
+
+class CloudDesc(ctypes.Structure):
+    """gwd_cloud_desc (include/gwdepth.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("depth", "labels", "sizes", "intrinsics", "region_map", "region_count", "planes", "source",
+                                               "poses", "workspace", "cloud", "cloud_offsets")] + \
+               [(n, ctypes.c_double) for n in ("min_depth", "max_depth", "edge")] + [("capacity", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("B", "Fh", "Fw", "max_regions", "stride", "normals", "keep", "has_frames")] + \
+               [("ext_h", ctypes.c_int32 * 16), ("ext_w", ctypes.c_int32 * 16), ("frames", RenderSlot)]
 
 
 class ResampleJob(ctypes.Structure):
@@ -355,6 +369,7 @@ class HipLibrary:
         L.gwd_fusion_planes.argtypes = [vp] * 5 + [i32] * 7 + [ctypes.c_double, i32, ctypes.c_double] + [vp] * 3
         L.gwd_fusion_depth.argtypes = [vp] * 8 + [i32] * 6 + [f32, f32] + [vp] * 4
         L.gwd_render_frames.argtypes = [ctypes.POINTER(RenderDesc), vp]
+        L.gwd_point_cloud.argtypes = [ctypes.POINTER(CloudDesc), vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1517,6 +1532,76 @@ class HipLibrary:
         every = [canvas, sizes, tables, lines, count, order, scores, kinds] + list(frames or []) + list(region_map or []) + \
             [t for views in list(planes) + list(label_planes) for t in views]
         self._check(self.lib.gwd_render_frames(ctypes.byref(d), self._stream(*every)), "gwd_render_frames")
+
+    @staticmethod
+    def cloud_desc(depth, labels, sizes, intrinsics, frames, region_map, region_count, planes, source, poses, frame_sizes, stride,
+                   min_depth, max_depth, edge, normals, keep, workspace, cloud, cloud_offsets):
+        """The gwd_cloud_desc of a call (no device work).  ext = what the host knows of every frame: the plane, the image handed over
+        for it and frame_sizes (None, or B (fh, fw) pairs).  Raises on a dtype, a layout or a size the kernels do not take."""
+        HipLibrary._typed("gwd_point_cloud", ((depth, torch.float32), (labels, torch.uint8), (sizes, torch.int32),
+                                              (intrinsics, torch.float64), (region_map, torch.uint8), (region_count, torch.int32),
+                                              (planes, torch.float64), (source, torch.uint8), (poses, torch.float64),
+                                              (workspace, torch.uint8), (cloud, torch.uint8), (cloud_offsets, torch.int32)))
+        if depth.dim() != 3:
+            raise ValueError("gwd_point_cloud: depth must be (B, Fh, Fw)")
+        B, Fh, Fw = depth.shape
+        shape = (B, Fh, Fw)
+        R = planes.shape[1] if planes is not None and planes.dim() == 3 else 0
+        if not 1 <= B <= 16 or tuple(labels.shape) != shape or tuple(sizes.shape) != (B, 2) or tuple(intrinsics.shape) != (B, 4) \
+                or any(t is not None and tuple(t.shape) != shape for t in (region_map, source)) \
+                or len({t is None for t in (region_map, region_count, planes)}) != 1 \
+                or (planes is not None and (tuple(planes.shape) != (B, R, 6) or region_count.numel() != B)) \
+                or (poses is not None and tuple(poses.shape) != (B, 3, 4)) or cloud.dim() != 2 or cloud.shape[1] != CLOUD_RECORD \
+                or cloud_offsets.numel() != B + 1 or (frame_sizes is not None and len(frame_sizes) != B) \
+                or not 1 <= int(stride) <= CLOUD_MAX_STRIDE:
+            raise ValueError("gwd_point_cloud: operand sizes do not match (B, Fh, Fw) = (%d, %d, %d)" % shape)
+        d = CloudDesc()
+        for n, t in (("depth", depth), ("labels", labels), ("sizes", sizes), ("intrinsics", intrinsics), ("region_map", region_map),
+                     ("region_count", region_count), ("planes", planes), ("source", source), ("poses", poses), ("workspace", workspace),
+                     ("cloud", cloud), ("cloud_offsets", cloud_offsets)):
+            setattr(d, n, None if t is None else _ptr(t).value)
+        d.min_depth, d.max_depth, d.edge = float(min_depth), float(max_depth), 0.0 if edge is None else float(edge)
+        d.capacity = cloud.shape[0]
+        d.B, d.Fh, d.Fw, d.max_regions, d.stride, d.normals, d.keep = B, Fh, Fw, R, int(stride), int(bool(normals)), CLOUD_KEEP[keep]
+        for b in range(B):
+            h, w = (Fh, Fw) if frame_sizes is None else (min(int(frame_sizes[b][0]), Fh), min(int(frame_sizes[b][1]), Fw))
+            if frames is not None:
+                t = frames[b]
+                if t.dtype != torch.uint8 or t.dim() != 3 or 0 in t.shape or t.shape[2] != 3 or t.stride(2) != 1 or t.stride(1) != 3 \
+                        or t.stride(0) >= 2 ** 31 or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
+                    raise ValueError("gwd_point_cloud: frames[%d] must be a uint8 (h, w, 3) view with dense rows, got %s %s strides %s"
+                                     % (b, t.dtype, tuple(t.shape), t.stride()))
+                d.frames.ptr[b], d.frames.pitch[b] = t.data_ptr(), max(t.stride(0), 1)
+                h, w = min(h, t.shape[0]), min(w, t.shape[1])
+            if h < 1 or w < 1:
+                raise ValueError("gwd_point_cloud: frame %d is empty (%d x %d)" % (b, h, w))
+            d.ext_h[b], d.ext_w[b] = h, w
+        d.has_frames = int(frames is not None)
+        return d
+
+    @staticmethod
+    def cloud_worst_case(desc):
+        """The points a call can yield at most: what its capacity must cover."""
+        s = desc.stride
+        return sum(-(-desc.ext_h[b] // s) * -(-desc.ext_w[b] // s) for b in range(desc.B))
+
+    def point_cloud(self, depth, labels, sizes, intrinsics, frames, region_map, region_count, planes, source, poses, frame_sizes, stride,
+                    min_depth, max_depth, edge, normals, keep, workspace, cloud, cloud_offsets):
+        """gwd_point_cloud: cloud (capacity, 32) uint8 and cloud_offsets (B + 1,) int32 out, every byte written.  depth float32 /
+        labels uint8 (B,Fh,Fw), sizes (B,2) int32, intrinsics (B,4) float64; frames: None or B uint8 (h,w,3) views; region_map uint8
+        (B,Fh,Fw) with region_count (B,) int32 and planes (B,R,6) float64, or all None; source uint8 (B,Fh,Fw), poses (B,3,4) float64
+        or None; frame_sizes: None or what the host knows of sizes; edge None or > 0; keep a key of CLOUD_KEEP; workspace: a uint8
+        tensor of workspace_bytes(WS_CLOUD, B, Fh, Fw, stride) bytes."""
+        d = self.cloud_desc(depth, labels, sizes, intrinsics, frames, region_map, region_count, planes, source, poses, frame_sizes, stride,
+                            min_depth, max_depth, edge, normals, keep, workspace, cloud, cloud_offsets)
+        if workspace.numel() < self.workspace_bytes(WS_CLOUD, d.B, d.Fh, d.Fw, d.stride):
+            raise ValueError("gwd_point_cloud: the workspace is smaller than workspace_bytes(WS_CLOUD, B, Fh, Fw, stride)")
+        if not self.cloud_worst_case(d) <= d.capacity <= 2 ** 31 - 1:
+            raise ValueError("gwd_point_cloud: a capacity of %d rows does not cover the %d points these frames can yield (or exceeds "
+                             "2^31 - 1)" % (d.capacity, self.cloud_worst_case(d)))
+        every = [depth, labels, sizes, intrinsics, region_map, region_count, planes, source, poses, workspace, cloud, cloud_offsets] + \
+            list(frames or [])
+        self._check(self.lib.gwd_point_cloud(ctypes.byref(d), self._stream(*every)), "gwd_point_cloud")
 
 
 _LIB = None

@@ -30,6 +30,9 @@ _FUSION_OPTIONS = ("ring", "gap", "trim", "min_ring", "max_rms", "align", "min_a
 FUSION_KEYS = ops.FUSION_KEYS                                          # ... with fusion=, by a call that passes sensor_depth=
 _RENDER_OPTIONS = ("panels", "width", "end_radius", "min_score", "score_range")
 RENDER_KEYS = ops.RENDER_KEYS                                          # ... with render=
+_CLOUD_OPTIONS = ("stride", "edge", "normals", "keep", "depth", "min_depth", "max_depth")
+_CLOUD_DEPTHS = ("auto", "depth", "depth_planar", "depth_fused")
+CLOUD_KEYS = ops.CLOUD_KEYS                                            # ... with cloud=, by a call that passes intrinsics=
 
 
 class InferenceSession:
@@ -101,12 +104,22 @@ class InferenceSession:
     default choice) or ("labels", "labels" | "region_map" | "fused_source" | "fusion_ring"), tint: such a uint8 name.  A panel that
     names a plane the session does not produce raises here.  predict() does not take part.
 
+    POINT CLOUD.  cloud=None (the default): nothing is allocated, predict_frames issues the launches and returns the keys it always did.
+    cloud=True or a dict (ops.point_cloud's options stride, edge, normals, keep; min_depth / max_depth default to the session's; depth:
+    "auto" - depth_fused when the call fused, else depth_planar when the session makes it, else depth - or one of those three by name;
+    a depth this session does not produce raises here): predict_frames(intrinsics=..., poses=None) also returns CLOUD_KEYS - the valid
+    pixels of every frame unprojected, packed frame after frame in raster order as 32-byte records (position, normal, the frame's
+    colour, label, region, fused_source, frame, flags: gw_depth_amd.cloud.fields) with their exclusive prefix, in three launches
+    (gwd_point_cloud) behind fusion and profiles and before render, on the session's stream, as fresh tensors, no host sync; the
+    uploaded frames are read where they lie, region_map / planes (pane normals) and fused_source take part when the session produces
+    them.  A call without intrinsics returns what it returns today.  predict() does not take part.
+
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
 
     def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6,
                  line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None, line_profiles=None, fusion=None,
-                 render=None):
+                 render=None, cloud=None):
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
         if line_nms_order not in ("score", "query"):
@@ -142,6 +155,7 @@ class InferenceSession:
         self.fusion = None if fusion is None else ops.check_fusion_options(
             **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(fusion if isinstance(fusion, dict) else {})))
         self.render = self._check_render(render)
+        self.cloud = self._check_cloud(cloud)
         self._cache = graphs.GraphCache()                  # every signature is captured at its first sight
         self._graphs = self._cache.entries                 # signature -> {"graph": chain of one, or None, ...}, least recently used first
         self._side = graphs.GraphSide()
@@ -232,6 +246,42 @@ class InferenceSession:
                                  count=post["nms_count" if nms else "count"][:B], order=None if nms else post["order"][:B],
                                  scores=post["nms_scores" if nms else "scores"][:B], kinds=res.get("profile_kind"),
                                  canvas_size=tuple(res["labels"].shape[1:]), **self.render["options"])
+
+    # ------------------------------------------------------------------ cloud=
+    def _check_cloud(self, cloud):
+        """cloud= -> None or dict(depth, options); the depth checked against what this session produces."""
+        if cloud is None:
+            return None
+        if cloud is not True and not isinstance(cloud, dict):
+            raise TypeError("cloud must be None, True or a dict of ops.point_cloud's options and depth, got %r" % (cloud,))
+        given = cloud if isinstance(cloud, dict) else {}
+        if set(given) - set(_CLOUD_OPTIONS):
+            raise TypeError("cloud: unknown option(s) %s (known: %s)" % (sorted(set(given) - set(_CLOUD_OPTIONS)), ", ".join(_CLOUD_OPTIONS)))
+        depth = given.get("depth", "auto")
+        planar = self.regions is not None and "depth_planar" in ops.region_keys(self.regions["planes"], self.regions["planar"])
+        names = ("depth",) + (("depth_planar",) if planar else ()) + (("depth_fused",) if self.fusion is not None else ())
+        if depth not in _CLOUD_DEPTHS:
+            raise ValueError("cloud: depth must be one of %s, got %r" % (", ".join(_CLOUD_DEPTHS), depth))
+        if depth != "auto" and depth not in names:
+            raise ValueError("cloud: depth names %r, this session produces %s" % (depth, ", ".join(names)))
+        options = ops.check_cloud_options(**dict({"min_depth": self.min_depth, "max_depth": self.max_depth},
+                                                 **{k: v for k, v in given.items() if k != "depth"}))
+        return dict(depth=depth, planar=planar, options=options)
+
+    def _cloud(self, frames, frame_sizes, res, intrinsics, poses):
+        """The cloud of one predict_frames call from the tensors it already holds."""
+        name = self.cloud["depth"]
+        if name == "auto":
+            name = "depth_fused" if "depth_fused" in res else "depth_planar" if self.cloud["planar"] else "depth"
+        if name not in res:
+            raise ValueError("predict_frames: cloud= names %r, which this call did not produce (sensor_depth=?)" % name)
+        panes = "planes" in res
+        Fh, Fw = res["labels"].shape[1:]
+        rows = ops.cloud_capacity(len(frames), Fh, Fw, self.cloud["options"]["stride"], frame_sizes)      # exact: the sizes are known here
+        return ops.point_cloud(res[name], res["labels"], res["sizes"], intrinsics, frames=frames,
+                               region_map=res["region_map"] if panes else None, region_count=res["region_count"] if panes else None,
+                               planes=res["planes"] if panes else None, source=res.get("fused_source"), poses=poses,
+                               frame_sizes=frame_sizes, capacity=rows, **self.cloud["options"])
 
     # ------------------------------------------------------------------ the reference passes `model`
     def eval(self):
@@ -447,7 +497,7 @@ class InferenceSession:
         return plane
 
     def predict_frames(self, frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False, intrinsics=None,
-                       sensor_depth=None):
+                       sensor_depth=None, poses=None):
         """Decoded camera frames in, results at each frame's own size out.  frames: list of uint8 (h,w,3) tensors, host or device,
         of any sizes: at most hip.AUGMENT_BATCH (16) per call, half that with ensemble=True (the forward batch is 2B); no side
         above 16384.  The reference's evaluation transform (RandomResize([size], max_size), ToTensor, Normalize:
@@ -463,11 +513,15 @@ class InferenceSession:
         A session with regions= adds REGION_KEYS (GLASS REGIONS above), at frame size.
 
         A session with line_profiles= adds PROFILE_KEYS (LINE PROFILES above); intrinsics: (B,4) (fx, fy, cx, cy) per frame at frame
-        size (a tensor or nested sequence) adds line_points - a session without line_profiles raises.
+        size (a tensor or nested sequence) adds line_points - a session with neither line_profiles= nor cloud= raises.
 
         A session with fusion= and sensor_depth - a list of B uint16 (h, w) tensors at each frame's own size, host or device, or one
         (B, Fh, Fw) uint16 tensor, millimetres, 0 = no reading - adds FUSION_KEYS (SENSOR FUSION above); sensor_depth without
         fusion= raises, a plane of another size than its frame raises and names the frame.
+
+        A session with cloud= and intrinsics adds CLOUD_KEYS (POINT CLOUD above); poses: (B,3,4) camera-to-world rows [R | t] per frame
+        (a tensor or nested sequence) puts the points and normals into world coordinates - poses without cloud=, or without
+        intrinsics, raise.
 
         A session with render= adds RENDER_KEYS (RENDER above).
 
@@ -486,12 +540,21 @@ class InferenceSession:
         if sensor_depth is not None and self.fusion is None:
             raise ValueError("predict_frames: sensor_depth needs a session built with fusion=")
         if intrinsics is not None:
-            if self.line_profiles is None:
-                raise ValueError("predict_frames: intrinsics need a session built with line_profiles=")
+            if self.line_profiles is None and self.cloud is None:
+                raise ValueError("predict_frames: intrinsics need a session built with line_profiles= or cloud=")
             intrinsics = torch.as_tensor(intrinsics, dtype=torch.float64)
             if tuple(intrinsics.shape) != (B, 4):
                 raise ValueError("predict_frames: intrinsics must be (%d, 4) = (fx, fy, cx, cy) per frame, got %s" % (B, tuple(intrinsics.shape)))
             intrinsics = intrinsics.to(dev, non_blocking=True)
+        if poses is not None:
+            if self.cloud is None:
+                raise ValueError("predict_frames: poses need a session built with cloud=")
+            if intrinsics is None:
+                raise ValueError("predict_frames: poses place a cloud, and a cloud needs intrinsics")
+            poses = poses.to(torch.float64) if torch.is_tensor(poses) else torch.from_numpy(np.asarray(poses, dtype=np.float64))
+            if tuple(poses.shape) != (B, 3, 4):
+                raise ValueError("predict_frames: poses must be (%d, 3, 4) = rows [R | t] per frame, got %s" % (B, tuple(poses.shape)))
+            poses = poses.to(dev, non_blocking=True)
         aug = data.DeviceAugment(train=False, test_size=size, max_size=max_size)
         frame_sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
         net_sizes = [data.resized_shape(w, h, size, max_size) for h, w in frame_sizes]
@@ -532,6 +595,9 @@ class InferenceSession:
             res.update(profiles)
         if fused is not None:
             res.update(fused)
+        if self.cloud is not None and intrinsics is not None:      # behind fusion and profiles, before render; the frames are read where they lie
+            with torch.no_grad(), self._on_stream():
+                res.update(self._cloud(on_dev[:B], frame_sizes, res, intrinsics, poses))
         if self.render is not None:                        # behind everything else, on the same stream; the uploaded frames are read where they are
             with torch.no_grad(), self._on_stream():
                 res["canvas"] = self._render(on_dev[:B], res, post, B, fused is not None)

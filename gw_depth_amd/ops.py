@@ -2349,16 +2349,16 @@ def _render_tables(tables, device):
     return t
 
 
-def _render_views(value, B, name):
+def _render_views(value, B, name, what="render_frames"):
     """One (B, h, w[, 3]) tensor or B separate views -> a list of B views (no copy)."""
     if value is None:
         return None
     if torch.is_tensor(value):
         if value.shape[0] != B:
-            raise ValueError("render_frames: %s holds %d frames, sizes %d" % (name, value.shape[0], B))
+            raise ValueError("%s: %s holds %d frames, sizes %d" % (what, name, value.shape[0], B))
         return [value[b] for b in range(B)]
     if not isinstance(value, (list, tuple)) or len(value) != B or not all(torch.is_tensor(t) for t in value):
-        raise ValueError("render_frames: %s is one tensor or a list of %d tensors" % (name, B))
+        raise ValueError("%s: %s is one tensor or a list of %d tensors" % (what, name, B))
     return list(value)
 
 
@@ -2429,3 +2429,109 @@ def render_frames(sizes, panels, frames=None, planes=None, label_planes=None, re
     _lib().render_frames(canvas, c(sizes), _render_tables(tables, dev), recs, frames, planes, label_planes, region_map, c(lines), c(count),
                          c(order), c(scores), c(kinds), opts)
     return canvas
+
+
+# ---------------------------------------------------------------------------------------------------------------------- point clouds
+CLOUD_KEYS = ("cloud", "cloud_offsets")
+CLOUD_FLAGS = {"point": 1, "normal": 2, "pane_normal": 4, "colour": 8}
+
+
+def check_cloud_options(stride=1, min_depth=1e-3, max_depth=10.0, edge=None, normals=True, keep="all"):
+    """Host validation of point_cloud's options (also what InferenceSession(cloud=...) accepts, next to `depth`); -> them as a dict."""
+    stride = _whole("stride", stride, "point_cloud")
+    if not 1 <= stride <= hip.CLOUD_MAX_STRIDE:
+        raise ValueError("point_cloud: 1 <= stride <= %d, got %r" % (hip.CLOUD_MAX_STRIDE, stride))
+    if not 0.0 < float(min_depth) < float(max_depth) < float("inf"):
+        raise ValueError("point_cloud: 0 < min_depth < max_depth, got %r, %r" % (min_depth, max_depth))
+    if edge is not None and not 0.0 < float(edge) < float("inf"):
+        raise ValueError("point_cloud: edge must be None or a relative depth jump > 0, got %r" % (edge,))
+    if not isinstance(normals, bool):
+        raise TypeError("point_cloud: normals must be True or False, got %r" % (normals,))
+    if keep not in hip.CLOUD_KEEP:
+        raise ValueError("point_cloud: keep must be one of %s, got %r" % (", ".join(repr(k) for k in hip.CLOUD_KEEP), keep))
+    return dict(stride=stride, min_depth=float(min_depth), max_depth=float(max_depth), edge=None if edge is None else float(edge),
+                normals=normals, keep=keep)
+
+
+def cloud_capacity(B, Fh, Fw, stride=1, frame_sizes=None):
+    """The rows a cloud needs at most: B planes of the stride lattice, or exactly that of frame_sizes ((fh, fw) pairs) when given."""
+    if frame_sizes is None:
+        frame_sizes = [(Fh, Fw)] * B
+    return sum(-(-min(int(h), Fh) // stride) * -(-min(int(w), Fw) // stride) for h, w in frame_sizes)
+
+
+def point_cloud(depth, labels, sizes, intrinsics, frames=None, region_map=None, region_count=None, planes=None, source=None, poses=None,
+                stride=1, min_depth=1e-3, max_depth=10.0, edge=None, normals=True, keep="all", capacity=None, frame_sizes=None):
+    """The scene in 3-D, on the device (gwd_point_cloud; tests/cloud_ref.py is the statement): depth (B,Fh,Fw)
+    float32 metres, labels uint8, sizes (B,2) int32 (fh, fw) on the device - what InferenceSession.predict_frames returns (depth may
+    as well be depth_planar or depth_fused) - and intrinsics (B,4) float64 (fx, fy, cx, cy) at frame size.  B <= 16, sides <= 16384.
+    frames: B uint8 (h,w,3) tensors as render_frames takes them (colour); region_map / region_count / planes of glass_regions (region
+    byte, pane normals); source: fused_source; poses (B,3,4) float64 camera-to-world rows [R | t].
+
+    The pixels (x, y) of a frame with x % stride == 0 and y % stride == 0 are candidates.  A candidate is a point when its depth is
+    finite and in [min_depth, max_depth], its label is not 255, keep ("all", "glass": label 1, "non_glass") admits the label and -
+    edge=e - no lattice neighbour with such a depth zn differs by more than e * min(zn, z) (the flying pixels at depth steps).
+    Position ((x - cx) z / fx, (y - cy) z / fy, z), through the pose when given; normals=True: a pixel of a pane with a fitted plane
+    takes the pane's normal in closed form (facing the camera), any other the normalised cross product of the differences of its
+    1-pixel neighbours' positions, oriented towards the camera; all in fp64, rounded once to float32.
+    -> dict in CLOUD_KEYS order: cloud (capacity, 32) uint8 - the points of frame 0 in raster order, then frame 1's, ...; a row is
+    float32 x y z nx ny nz, uint8 red green blue label region source frame flags (CLOUD_FLAGS; gw_depth_amd.cloud.fields gives the
+    views); every row behind the last point is 32 zero bytes (flags 0 = no point) - and cloud_offsets (B+1,) int32, the exclusive
+    prefix of the frames' counts, [B] the total.  capacity defaults to B * ceil(Fh / stride) * ceil(Fw / stride); frame_sizes: what
+    the host knows of `sizes` (B (fh, fw) pairs; a frame's image bounds it as well) - with it a capacity may go down to
+    cloud_capacity(B, Fh, Fw, stride, frame_sizes), the most these frames can yield; a smaller one raises here, the kernels never
+    truncate.  Fresh tensors, no host sync; repeated calls give bit-identical results."""
+    opt = check_cloud_options(stride, min_depth, max_depth, edge, normals, keep)
+    for name, t, dt in (("depth", depth, torch.float32), ("labels", labels, torch.uint8), ("sizes", sizes, torch.int32),
+                        ("intrinsics", intrinsics, torch.float64)):
+        if not torch.is_tensor(t) or t.dtype != dt:
+            raise TypeError("point_cloud: %s must be a %s tensor" % (name, dt))
+    for name, t, dt in (("region_map", region_map, torch.uint8), ("region_count", region_count, torch.int32),
+                        ("planes", planes, torch.float64), ("source", source, torch.uint8), ("poses", poses, torch.float64)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dt):
+            raise TypeError("point_cloud: %s must be a %s tensor" % (name, dt))
+    if depth.dim() != 3 or 0 in depth.shape:
+        raise ValueError("point_cloud: depth must be (B, Fh, Fw), got %s" % (tuple(depth.shape),))
+    B, Fh, Fw = depth.shape
+    if B > hip.AUGMENT_BATCH or max(Fh, Fw) > 16384:
+        raise ValueError("point_cloud: at most %d frames of at most 16384 per side, got %s" % (hip.AUGMENT_BATCH, tuple(depth.shape)))
+    for name, t in (("labels", labels), ("region_map", region_map), ("source", source)):
+        if t is not None and tuple(t.shape) != (B, Fh, Fw):
+            raise ValueError("point_cloud: %s must be %s like depth, got %s" % (name, (B, Fh, Fw), tuple(t.shape)))
+    if tuple(sizes.shape) != (B, 2) or tuple(intrinsics.shape) != (B, 4):
+        raise ValueError("point_cloud: sizes must be (%d, 2) and intrinsics (%d, 4)" % (B, B))
+    if len({t is None for t in (region_map, region_count, planes)}) != 1:
+        raise ValueError("point_cloud: region_map, region_count and planes come together (ops.glass_regions with planes=True)")
+    if planes is not None and (tuple(region_count.shape) != (B,) or planes.dim() != 3 or planes.shape[0] != B or planes.shape[2] != 6
+                               or not 1 <= planes.shape[1] <= hip.REGION_MAX):
+        raise ValueError("point_cloud: region_count must be (%d,) and planes (%d, 1..%d, 6)" % (B, B, hip.REGION_MAX))
+    if poses is not None and tuple(poses.shape) != (B, 3, 4):
+        raise ValueError("point_cloud: poses must be (%d, 3, 4) = rows [R | t] per frame, got %s" % (B, tuple(poses.shape)))
+    frames = _render_views(frames, B, "frames", "point_cloud")
+    if frames is not None:                                # a frame is read where it lies when its pixels are dense, whatever its row pitch
+        if any(f.dtype != torch.uint8 for f in frames):
+            raise TypeError("point_cloud: frames must be %s" % torch.uint8)
+        frames = [f if f.dim() != 3 or (f.stride(2) == 1 and f.stride(1) == 3) else f.contiguous() for f in frames]
+    if frame_sizes is not None:
+        frame_sizes = [(int(h), int(w)) for h, w in frame_sizes]
+        if len(frame_sizes) != B or any(h < 1 or w < 1 for h, w in frame_sizes):
+            raise ValueError("point_cloud: frame_sizes is %d pairs (fh, fw) >= 1" % B)
+    if frames is not None and all(f.dim() == 3 for f in frames):      # a frame's image bounds it too
+        known = frame_sizes or [(Fh, Fw)] * B
+        frame_sizes = [(min(h, f.shape[0]), min(w, f.shape[1])) for (h, w), f in zip(known, frames)]
+    worst = cloud_capacity(B, Fh, Fw, opt["stride"], frame_sizes)
+    capacity = cloud_capacity(B, Fh, Fw, opt["stride"]) if capacity is None else _whole("capacity", capacity, "point_cloud")
+    if capacity < worst:
+        raise ValueError("point_cloud: a capacity of %d rows is below the %d points these frames can yield at stride %d: the cloud is "
+                         "never shortened" % (capacity, worst, opt["stride"]))
+    if capacity > 2 ** 31 - 1:
+        raise ValueError("point_cloud: a capacity of %d rows exceeds 2^31 - 1 (a larger stride, fewer frames per call)" % capacity)
+    lib, dev = _lib(), depth.device
+    c = lambda t: None if t is None else t.contiguous()
+    ws = torch.empty(lib.workspace_bytes(hip.WS_CLOUD, B, Fh, Fw, opt["stride"]), dtype=torch.uint8, device=dev)
+    res = {"cloud": torch.empty((capacity, hip.CLOUD_RECORD), dtype=torch.uint8, device=dev),
+           "cloud_offsets": torch.empty((B + 1,), dtype=torch.int32, device=dev)}
+    lib.point_cloud(c(depth), c(labels), c(sizes), c(intrinsics), frames, c(region_map), c(region_count), c(planes), c(source), c(poses),
+                    frame_sizes, opt["stride"], opt["min_depth"], opt["max_depth"], opt["edge"], opt["normals"], opt["keep"], ws,
+                    res["cloud"], res["cloud_offsets"])
+    return res

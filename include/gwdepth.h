@@ -90,9 +90,10 @@ const char *gwd_arch(void);
  *   GWD_WS_HEALTH          dims = {n_chunks}       -> `partial` of gwd_segment_stats
  *   GWD_WS_REGIONS         dims = {B, Fh, Fw, max_candidates} -> `workspace` of gwd_glass_regions / gwd_region_planes
  *   GWD_WS_FUSION          dims = {B, Fh, Fw}      -> `workspace` of gwd_fusion_ring / gwd_fusion_planes
+ *   GWD_WS_CLOUD           dims = {B, Fh, Fw, stride} -> `workspace` of gwd_point_cloud
  * Returns -1 for an unknown op or a wrong dimension count.                                                     */
 enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3, GWD_WS_HEALTH = 4, GWD_WS_REGIONS = 5,
-       GWD_WS_FUSION = 6 };
+       GWD_WS_FUSION = 6, GWD_WS_CLOUD = 7 };
 int64_t gwd_query_workspace(int32_t op, const int64_t *dims, int32_t ndims);
 
 /* Implicit-GEMM convolution on MFMA with fused epilogue y = act(scale*conv(x,w) + shift + residual).
@@ -1130,6 +1131,65 @@ typedef struct gwd_render_desc {
     gwd_render_panel panels[GWD_RENDER_MAX_PANELS];
 } gwd_render_desc;
 int gwd_render_frames(const gwd_render_desc *desc, void *stream);
+
+/* Point clouds of predict_frames' results (csrc/cloud.hip): every frame's dense depth unprojected through its
+ * pinhole intrinsics, the valid points packed frame after frame in raster order; tests/cloud_ref.py states the same in numpy.
+ * depth [B][Fh][Fw] fp32 metres, labels [B][Fh][Fw] uint8, sizes [B][2] int32 (fh, fw) on the DEVICE, intrinsics [B][4] fp64
+ * (fx, fy, cx, cy) at frame size.  Optional (NULL: absent): region_map uint8 / region_count [B] int32 / planes [B][max_regions][6]
+ * fp64 of gwd_glass_regions / gwd_region_planes (all three or none), source [B][Fh][Fw] uint8 (fused_source), poses [B][3][4] fp64
+ * camera-to-world rows [R | t], frames (has_frames != 0): B uint8 RGB images, a pointer and a row pitch in bytes each, 3 bytes per
+ * pixel.  ext_h / ext_w [B]: what the HOST knows frame b cannot exceed (1 .. Fh, 1 .. Fw; at most what its image covers): sizes is
+ * clamped to it, so nothing is read outside an operand whatever sizes holds.  B <= 16, Fh, Fw <= 16384.
+ *   candidates  pixel (x, y) of frame b with x < fw, y < fh, x % stride == 0, y % stride == 0 (1 <= stride <= GWD_CLOUD_MAX_STRIDE).
+ *   a point     z = depth finite with min_depth <= z <= max_depth (compared in fp64); label != 255; keep admits the label
+ *               (GWD_CLOUD_KEEP_GLASS: label == 1, GWD_CLOUD_KEEP_NON_GLASS: label != 1); with edge > 0 every lattice neighbour
+ *               (+- stride in x or y, inside the frame) with such a depth zn has |zn - z| <= edge * min(zn, z) in fp64.
+ *   position    X = ((x - cx) z) / fx, Y = ((y - cy) z) / fy, Z = z; with poses Pw_i = ((r_i0 X + r_i1 Y) + r_i2 Z) + t_i; fp64, one
+ *               rounding per operation, one rounding to fp32.
+ *   normal      (normals != 0; otherwise zeros) a pixel whose region_map value is r + 1 with r < region_count[b], planes[b][r]
+ *               of status 0 and m = (alpha fx, beta fy, (gamma + alpha cx) + beta cy) of finite length > 0: -m / |m|.  Any other
+ *               pixel: dx x dy of the unprojected camera positions of its 1-pixel neighbours - per axis the central difference where
+ *               both neighbours lie in the frame with a depth as above, else the one-sided one that exists - normalised, negated
+ *               when n . P > 0; an axis without a neighbour or a cross product of length 0: zeros.  Rotated by R with poses.
+ *   record      32 bytes: fp32 x y z nx ny nz; uint8 red green blue (0 without frames), label, region (region_map or 0), source
+ *               (or 0), frame (b), flags: 1 a point, 2 has a normal, 4 the normal is a pane's, 8 has colour.
+ * cloud [capacity][32] uint8, 16-byte aligned: the points of frame 0 in raster order, then frame 1's, ...; cloud_offsets [B + 1]
+ * int32: the exclusive prefix of the frames' counts, [B] the total; every row from the total on is written as 32 zero bytes.
+ * capacity must cover the sum over b of ceil(ext_h / stride) * ceil(ext_w / stride) and be at most 2^31 - 1: -1 otherwise, the
+ * kernels never truncate.  workspace: gwd_query_workspace(GWD_WS_CLOUD, {B, Fh, Fw, stride}) bytes, 16-byte aligned, needs no
+ * initialisation.  Three launches: one workgroup per GWD_CLOUD_TILE candidates of one frame counts its points; one workgroup turns
+ * the counts into exclusive offsets; the first grid again ranks its points by ballot and stores them, two 16-byte stores each, and
+ * zeroes the tail.  No workgroup waits for another, no atomics, no memset, no host synchronisation; bit-identical from call to call;
+ * a frame's rows depend on neither its slot nor its neighbours nor Fh x Fw.
+ * -1 on a null pointer or a size / capacity / range outside its limits, -2 on a keep outside its enum, an incomplete region
+ * triple, max_regions outside 1 .. GWD_REGION_MAX or edge NaN, -3 when a pointer is not aligned to its element (workspace and
+ * cloud: 16 bytes); nothing is launched then.                                                                                 */
+#define GWD_CLOUD_TILE 1024
+#define GWD_CLOUD_RECORD 32
+#define GWD_CLOUD_MAX_STRIDE 16
+#define GWD_CLOUD_KEEP_ALL 0
+#define GWD_CLOUD_KEEP_GLASS 1
+#define GWD_CLOUD_KEEP_NON_GLASS 2
+typedef struct gwd_cloud_desc {
+    const float *depth;
+    const uint8_t *labels;
+    const int32_t *sizes;
+    const double *intrinsics;
+    const uint8_t *region_map;
+    const int32_t *region_count;
+    const double *planes;
+    const uint8_t *source;
+    const double *poses;
+    void *workspace;
+    uint8_t *cloud;
+    int32_t *cloud_offsets;
+    double min_depth, max_depth, edge;                    /* edge <= 0: no edge rule */
+    int64_t capacity;
+    int32_t B, Fh, Fw, max_regions, stride, normals, keep, has_frames;
+    int32_t ext_h[16], ext_w[16];
+    gwd_render_slot frames;
+} gwd_cloud_desc;
+int gwd_point_cloud(const gwd_cloud_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }
