@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GWD_LIB") or os.path.join(_HERE, "libgwdepth_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3, 4
-WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS, WS_FUSION, WS_CLOUD = 0, 1, 2, 3, 4, 5, 6, 7          # gwd_query_workspace ops
+WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS, WS_FUSION, WS_CLOUD, WS_SCENE = 0, 1, 2, 3, 4, 5, 6, 7, 8          # gwd_query_workspace ops
 GATHER_CONV, GATHER_TRANSPOSED, GATHER_UPSAMPLED = 0, 1, 2
 RESAMPLE_BILINEAR_AC, RESAMPLE_NEAREST = 0, 1
 
@@ -48,6 +48,7 @@ ENTRY_POINTS = [
     "gwd_fusion_ring", "gwd_fusion_planes", "gwd_fusion_depth",
     "gwd_render_frames",
     "gwd_point_cloud",
+    "gwd_scene_reset", "gwd_scene_integrate", "gwd_scene_extract",
 ]
 
 
@@ -146,6 +147,11 @@ CLOUD_TILE = 1024         # GWD_CLOUD_TILE: candidates of one frame per workgrou
 CLOUD_RECORD = 32         # GWD_CLOUD_RECORD: bytes of a point
 CLOUD_MAX_STRIDE = 16     # GWD_CLOUD_MAX_STRIDE
 CLOUD_KEEP = {"all": 0, "glass": 1, "non_glass": 2}       # GWD_CLOUD_KEEP_*
+SCENE_TILE = 1024         # GWD_SCENE_TILE: rows (integrate) or ranks (extract) per workgroup
+SCENE_VOXEL_BYTES = 128   # GWD_SCENE_VOXEL_BYTES: the accumulators of one voxel
+SCENE_MAX_VOXELS = 1 << 27    # GWD_SCENE_MAX_VOXELS
+SCENE_FLAG_MERGED = 16    # GWD_SCENE_FLAG_MERGED
+SCENE_STATE = ("serial", "count", "points", "dropped", "status")      # the first five int64 of gwd_scene_desc.state
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
 COLOR_ADJUST, COLOR_SUMS = 0, 1
 
@@ -179,6 +185,12 @@ class CloudDesc(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("min_depth", "max_depth", "edge")] + [("capacity", ctypes.c_int64)] + \
                [(n, ctypes.c_int32) for n in ("B", "Fh", "Fw", "max_regions", "stride", "normals", "keep", "has_frames")] + \
                [("ext_h", ctypes.c_int32 * 16), ("ext_w", ctypes.c_int32 * 16), ("frames", RenderSlot)]
+
+
+class SceneDesc(ctypes.Structure):
+    """gwd_scene_desc (include/gwdepth.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("keys", "marks", "ranks", "voxels", "state")] + \
+               [("voxel", ctypes.c_double), ("origin", ctypes.c_double * 3), ("max_voxels", ctypes.c_int64), ("slots", ctypes.c_int64)]
 
 
 class ResampleJob(ctypes.Structure):
@@ -370,6 +382,9 @@ class HipLibrary:
         L.gwd_fusion_depth.argtypes = [vp] * 8 + [i32] * 6 + [f32, f32] + [vp] * 4
         L.gwd_render_frames.argtypes = [ctypes.POINTER(RenderDesc), vp]
         L.gwd_point_cloud.argtypes = [ctypes.POINTER(CloudDesc), vp]
+        L.gwd_scene_reset.argtypes = [ctypes.POINTER(SceneDesc), vp]
+        L.gwd_scene_integrate.argtypes = [ctypes.POINTER(SceneDesc), vp, vp, i64, i32, vp, vp]
+        L.gwd_scene_extract.argtypes = [ctypes.POINTER(SceneDesc), i32, i32, vp, vp, vp, vp, vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1602,6 +1617,67 @@ class HipLibrary:
         every = [depth, labels, sizes, intrinsics, region_map, region_count, planes, source, poses, workspace, cloud, cloud_offsets] + \
             list(frames or [])
         self._check(self.lib.gwd_point_cloud(ctypes.byref(d), self._stream(*every)), "gwd_point_cloud")
+
+    @staticmethod
+    def scene_desc(keys, marks, ranks, voxels, state, voxel, origin):
+        """The gwd_scene_desc of a map (no device work): keys / marks (slots,) int64, ranks (slots,) int32, voxels (max_voxels,
+        SCENE_VOXEL_BYTES) uint8, state (8,) int64, all contiguous.  Raises on a dtype, a size or a parameter the kernels do not take."""
+        HipLibrary._typed("gwd_scene", ((keys, torch.int64), (marks, torch.int64), (ranks, torch.int32), (voxels, torch.uint8),
+                                        (state, torch.int64)))
+        if any(t is None or not t.is_contiguous() for t in (keys, marks, ranks, voxels, state)):
+            raise ValueError("gwd_scene: the map's five tensors are contiguous")
+        slots = keys.numel()
+        if keys.dim() != 1 or tuple(marks.shape) != (slots,) or tuple(ranks.shape) != (slots,) or voxels.dim() != 2 \
+                or voxels.shape[1] != SCENE_VOXEL_BYTES or tuple(state.shape) != (8,):
+            raise ValueError("gwd_scene: keys / marks / ranks are (slots,), voxels (max_voxels, %d), state (8,)" % SCENE_VOXEL_BYTES)
+        max_voxels = voxels.shape[0]
+        if not 1 <= max_voxels <= SCENE_MAX_VOXELS or slots <= max_voxels or slots > 2 * SCENE_MAX_VOXELS or slots & (slots - 1):
+            raise ValueError("gwd_scene: 1 <= max_voxels <= 2^27 < slots, a power of two <= 2^28; got %d, %d" % (max_voxels, slots))
+        voxel, origin = float(voxel), [float(v) for v in origin]
+        if not 0.0 < voxel < float("inf") or len(origin) != 3 or not all(abs(v) < float("inf") for v in origin):
+            raise ValueError("gwd_scene: voxel is finite and > 0, origin three finite numbers; got %r, %r" % (voxel, origin))
+        d = SceneDesc()
+        d.keys, d.marks, d.ranks, d.voxels, d.state = (_ptr(t).value for t in (keys, marks, ranks, voxels, state))
+        d.voxel, d.max_voxels, d.slots = voxel, max_voxels, slots
+        for k in range(3):
+            d.origin[k] = origin[k]
+        return d
+
+    @staticmethod
+    def scene_cloud_check(what, cloud, cloud_offsets):
+        HipLibrary._typed(what, ((cloud, torch.uint8), (cloud_offsets, torch.int32)))
+        if cloud is None or cloud_offsets is None or cloud.dim() != 2 or cloud.shape[1] != CLOUD_RECORD or cloud_offsets.dim() != 1 \
+                or not cloud.is_contiguous() or not cloud_offsets.is_contiguous():
+            raise ValueError("%s: cloud is a contiguous (rows, %d) uint8 tensor, cloud_offsets a contiguous int32 vector" % (what, CLOUD_RECORD))
+
+    def scene_reset(self, desc, tensors):
+        """gwd_scene_reset: desc of scene_desc, tensors the map's five (for the device check)."""
+        self._check(self.lib.gwd_scene_reset(ctypes.byref(desc), self._stream(*tensors)), "gwd_scene_reset")
+
+    def scene_integrate(self, desc, tensors, cloud, cloud_offsets, workspace):
+        """gwd_scene_integrate: cloud (rows >= 1, 32) uint8 and cloud_offsets (>= 2,) int32 of point_cloud (or of an extraction) into
+        the map; workspace: a uint8 tensor of workspace_bytes(WS_SCENE, rows, max_voxels) bytes."""
+        self.scene_cloud_check("gwd_scene_integrate", cloud, cloud_offsets)
+        if cloud.shape[0] < 1 or cloud.shape[0] > 2 ** 31 - 1 or cloud_offsets.numel() < 2:
+            raise ValueError("gwd_scene_integrate: 1 <= rows <= 2^31 - 1 and at least two offsets, got %d, %d" % (cloud.shape[0], cloud_offsets.numel()))
+        if workspace.numel() < self.workspace_bytes(WS_SCENE, cloud.shape[0], desc.max_voxels):
+            raise ValueError("gwd_scene_integrate: the workspace is smaller than workspace_bytes(WS_SCENE, rows, max_voxels)")
+        self._check(self.lib.gwd_scene_integrate(ctypes.byref(desc), _ptr(cloud), _ptr(cloud_offsets), cloud.shape[0], cloud_offsets.numel(),
+                                                 _ptr(workspace), self._stream(cloud, cloud_offsets, workspace, *tensors)), "gwd_scene_integrate")
+
+    def scene_extract(self, desc, tensors, min_obs, keep, workspace, cloud, cloud_offsets, voxel_stats):
+        """gwd_scene_extract: cloud (max_voxels, 32) uint8, cloud_offsets (2,) int32 and voxel_stats (max_voxels, 4) int32 out, every
+        byte written; keep a key of CLOUD_KEEP; workspace as for scene_integrate (any rows)."""
+        self.scene_cloud_check("gwd_scene_extract", cloud, cloud_offsets)
+        self._typed("gwd_scene_extract", ((voxel_stats, torch.int32),))
+        if cloud.shape[0] != desc.max_voxels or cloud_offsets.numel() != 2 or tuple(voxel_stats.shape) != (desc.max_voxels, 4) \
+                or not voxel_stats.is_contiguous() or not 1 <= int(min_obs) <= 2 ** 31 - 1:
+            raise ValueError("gwd_scene_extract: cloud (max_voxels, 32), cloud_offsets (2,), voxel_stats (max_voxels, 4), min_obs >= 1")
+        if workspace.numel() < self.workspace_bytes(WS_SCENE, 1, desc.max_voxels):
+            raise ValueError("gwd_scene_extract: the workspace is smaller than workspace_bytes(WS_SCENE, 1, max_voxels)")
+        self._check(self.lib.gwd_scene_extract(ctypes.byref(desc), int(min_obs), CLOUD_KEEP[keep], _ptr(workspace), _ptr(cloud),
+                                               _ptr(cloud_offsets), _ptr(voxel_stats),
+                                               self._stream(workspace, cloud, cloud_offsets, voxel_stats, *tensors)), "gwd_scene_extract")
 
 
 _LIB = None

@@ -33,6 +33,7 @@ RENDER_KEYS = ops.RENDER_KEYS                                          # ... wit
 _CLOUD_OPTIONS = ("stride", "edge", "normals", "keep", "depth", "min_depth", "max_depth")
 _CLOUD_DEPTHS = ("auto", "depth", "depth_planar", "depth_fused")
 CLOUD_KEYS = ops.CLOUD_KEYS                                            # ... with cloud=, by a call that passes intrinsics=
+_SCENE_OPTIONS = ("voxel", "max_voxels", "origin", "slots")
 
 
 class InferenceSession:
@@ -114,12 +115,19 @@ class InferenceSession:
     uploaded frames are read where they lie, region_map / planes (pane normals) and fused_source take part when the session produces
     them.  A call without intrinsics returns what it returns today.  predict() does not take part.
 
+    SCENE MAP.  scene=None (the default): nothing is allocated or launched, predict_frames returns the keys it always did.  scene=a
+    gw_depth_amd.cloud.SceneMap, or a dict (voxel, max_voxels, origin, slots) from which one is built on the model's device, needs
+    cloud=: predict_frames(intrinsics=..., poses=...) integrates the call's cloud into sess.scene (five launches, gwd_scene_integrate)
+    behind the cloud and before render, on the session's stream, no host sync; the returned keys do not change - sess.scene.extract()
+    gives the merged map whenever it is wanted.  A call with intrinsics but without poses raises: camera-frame clouds share no world.
+    A call without intrinsics returns what it returns today and leaves the map alone.  predict() does not take part.
+
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
 
     def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6,
                  line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None, line_profiles=None, fusion=None,
-                 render=None, cloud=None):
+                 render=None, cloud=None, scene=None):
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
         if line_nms_order not in ("score", "query"):
@@ -156,6 +164,7 @@ class InferenceSession:
             **dict({"min_depth": self.min_depth, "max_depth": self.max_depth}, **(fusion if isinstance(fusion, dict) else {})))
         self.render = self._check_render(render)
         self.cloud = self._check_cloud(cloud)
+        self.scene = self._check_scene(scene)
         self._cache = graphs.GraphCache()                  # every signature is captured at its first sight
         self._graphs = self._cache.entries                 # signature -> {"graph": chain of one, or None, ...}, least recently used first
         self._side = graphs.GraphSide()
@@ -282,6 +291,24 @@ class InferenceSession:
                                region_map=res["region_map"] if panes else None, region_count=res["region_count"] if panes else None,
                                planes=res["planes"] if panes else None, source=res.get("fused_source"), poses=poses,
                                frame_sizes=frame_sizes, capacity=rows, **self.cloud["options"])
+
+    # ------------------------------------------------------------------ scene=
+    def _check_scene(self, scene):
+        """scene= -> None or a cloud.SceneMap (the one handed over, or one built from a dict of its parameters)."""
+        from . import cloud as PC
+        if scene is None:
+            return None
+        if not isinstance(scene, (dict, PC.SceneMap)):
+            raise TypeError("scene must be None, a gw_depth_amd.cloud.SceneMap or a dict of its parameters, got %r" % (scene,))
+        if self.cloud is None:
+            raise ValueError("scene= needs a session built with cloud= (the map is made of the calls' clouds)")
+        if isinstance(scene, PC.SceneMap):
+            return scene
+        if set(scene) - set(_SCENE_OPTIONS):
+            raise TypeError("scene: unknown option(s) %s (known: %s)" % (sorted(set(scene) - set(_SCENE_OPTIONS)), ", ".join(_SCENE_OPTIONS)))
+        if "voxel" not in scene or "max_voxels" not in scene:
+            raise TypeError("scene: a dict names voxel and max_voxels")
+        return PC.SceneMap(device=self._device(), **scene)      # validates before anything is allocated or launched
 
     # ------------------------------------------------------------------ the reference passes `model`
     def eval(self):
@@ -521,7 +548,8 @@ class InferenceSession:
 
         A session with cloud= and intrinsics adds CLOUD_KEYS (POINT CLOUD above); poses: (B,3,4) camera-to-world rows [R | t] per frame
         (a tensor or nested sequence) puts the points and normals into world coordinates - poses without cloud=, or without
-        intrinsics, raise.
+        intrinsics, raise.  A session with scene= also integrates that cloud into sess.scene (SCENE MAP above) and takes no
+        intrinsics without poses.
 
         A session with render= adds RENDER_KEYS (RENDER above).
 
@@ -555,6 +583,8 @@ class InferenceSession:
             if tuple(poses.shape) != (B, 3, 4):
                 raise ValueError("predict_frames: poses must be (%d, 3, 4) = rows [R | t] per frame, got %s" % (B, tuple(poses.shape)))
             poses = poses.to(dev, non_blocking=True)
+        if self.scene is not None and intrinsics is not None and poses is None:
+            raise ValueError("predict_frames: a session with scene= needs poses with its intrinsics: camera-frame clouds share no world")
         aug = data.DeviceAugment(train=False, test_size=size, max_size=max_size)
         frame_sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
         net_sizes = [data.resized_shape(w, h, size, max_size) for h, w in frame_sizes]
@@ -598,6 +628,8 @@ class InferenceSession:
         if self.cloud is not None and intrinsics is not None:      # behind fusion and profiles, before render; the frames are read where they lie
             with torch.no_grad(), self._on_stream():
                 res.update(self._cloud(on_dev[:B], frame_sizes, res, intrinsics, poses))
+                if self.scene is not None:                 # behind the cloud, before render; the map is the session's, not the call's
+                    self.scene.integrate(res["cloud"], res["cloud_offsets"])
         if self.render is not None:                        # behind everything else, on the same stream; the uploaded frames are read where they are
             with torch.no_grad(), self._on_stream():
                 res["canvas"] = self._render(on_dev[:B], res, post, B, fused is not None)

@@ -2535,3 +2535,32 @@ def point_cloud(depth, labels, sizes, intrinsics, frames=None, region_map=None, 
                     frame_sizes, opt["stride"], opt["min_depth"], opt["max_depth"], opt["edge"], opt["normals"], opt["keep"], ws,
                     res["cloud"], res["cloud_offsets"])
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------- scene map
+SCENE_KEYS = ("cloud", "cloud_offsets", "voxel_stats")
+
+
+def check_scene_options(voxel, max_voxels, origin=(0.0, 0.0, 0.0), slots=None, min_obs=1, keep="all"):
+    """Host validation of scene_merge's options (gw_depth_amd.cloud.SceneMap's parameters and extract's); -> them as a dict."""
+    from . import cloud as _cloud
+    voxel, max_voxels, origin, slots = _cloud.check_scene_parameters(voxel, max_voxels, origin, slots)
+    return dict(voxel=voxel, max_voxels=max_voxels, origin=origin, slots=slots, **_cloud.check_extract_options(min_obs, keep))
+
+
+def scene_merge(cloud, cloud_offsets, voxel, max_voxels=None, origin=(0.0, 0.0, 0.0), slots=None, min_obs=1, keep="all"):
+    """One cloud merged into voxels of `voxel` metres, on the device (gwd_scene_*; tests/scene_ref.py is the
+    statement): reset + integrate + extract on a throw-away gw_depth_amd.cloud.SceneMap - the device's np.unique over quantised
+    positions.  cloud (rows, 32) uint8 / cloud_offsets (B+1,) int32 of point_cloud, in one world (poses=).  max_voxels defaults to
+    the cloud's rows (a cloud cannot fill more).  -> dict in SCENE_KEYS order as SceneMap.extract returns it; with more than
+    max_voxels voxels the cloud is EMPTY (cloud_offsets [0, 0]), never truncated.  No host sync.  A stream of calls keeps one
+    SceneMap instead."""
+    from . import cloud as _cloud
+    if not torch.is_tensor(cloud) or cloud.dtype != torch.uint8 or cloud.dim() != 2 or cloud.shape[1] != hip.CLOUD_RECORD:
+        raise TypeError("scene_merge: cloud must be a (rows, %d) uint8 tensor" % hip.CLOUD_RECORD)
+    if max_voxels is None:
+        max_voxels = max(int(cloud.shape[0]), 1)
+    opt = check_scene_options(voxel, max_voxels, origin, slots, min_obs, keep)
+    _cloud.check_integrate_operands(cloud, cloud_offsets)
+    m = _cloud.SceneMap(opt["voxel"], opt["max_voxels"], opt["origin"], opt["slots"], device=cloud.device)
+    return m.integrate(cloud, cloud_offsets).extract(opt["min_obs"], opt["keep"])

@@ -91,9 +91,10 @@ const char *gwd_arch(void);
  *   GWD_WS_REGIONS         dims = {B, Fh, Fw, max_candidates} -> `workspace` of gwd_glass_regions / gwd_region_planes
  *   GWD_WS_FUSION          dims = {B, Fh, Fw}      -> `workspace` of gwd_fusion_ring / gwd_fusion_planes
  *   GWD_WS_CLOUD           dims = {B, Fh, Fw, stride} -> `workspace` of gwd_point_cloud
+ *   GWD_WS_SCENE           dims = {rows, max_voxels} -> `workspace` of gwd_scene_integrate (a cloud of `rows` rows) / gwd_scene_extract
  * Returns -1 for an unknown op or a wrong dimension count.                                                     */
 enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3, GWD_WS_HEALTH = 4, GWD_WS_REGIONS = 5,
-       GWD_WS_FUSION = 6, GWD_WS_CLOUD = 7 };
+       GWD_WS_FUSION = 6, GWD_WS_CLOUD = 7, GWD_WS_SCENE = 8 };
 int64_t gwd_query_workspace(int32_t op, const int64_t *dims, int32_t ndims);
 
 /* Implicit-GEMM convolution on MFMA with fused epilogue y = act(scale*conv(x,w) + shift + residual).
@@ -1190,6 +1191,62 @@ typedef struct gwd_cloud_desc {
     gwd_render_slot frames;
 } gwd_cloud_desc;
 int gwd_point_cloud(const gwd_cloud_desc *desc, void *stream);
+
+/* Scene map (csrc/scene.hip): the clouds of gwd_point_cloud, in world coordinates (poses), merged call after
+ * call into one persistent voxel grid on the device - one merged record per occupied voxel, in the order the voxels were first seen;
+ * tests/scene_ref.py states the same in numpy.  The map is the caller's memory, described by gwd_scene_desc; the library keeps nothing.
+ *   keys, marks [slots] uint64, ranks [slots] int32: an open-addressing table; slots a power of two, max_voxels < slots <=
+ *               2 * GWD_SCENE_MAX_VOXELS.  voxels [max_voxels][GWD_SCENE_VOXEL_BYTES] bytes, 16-byte aligned: the integer accumulators
+ *               of the voxel of each rank.  state [8] int64: serial (calls integrated), count (voxels), points (rows taken in),
+ *               dropped (rows refused), status (0 ok, 1 overflow), three spare.  voxel: the edge in metres, finite and > 0; origin
+ *               [3] finite; 1 <= max_voxels <= GWD_SCENE_MAX_VOXELS.  All of it is undefined until gwd_scene_reset has run.
+ * gwd_scene_reset      one launch: an empty map, state all zero.
+ * gwd_scene_integrate  cloud [rows][32] uint8 (16-byte aligned) records of gwd_point_cloud, cloud_offsets [n_offsets] int32 on the
+ *                      DEVICE, n_offsets >= 2: only its last entry, the total, is read (clamped to 0 .. rows); 1 <= rows <= 2^31 - 1.
+ *                      Row r < total is DROPPED (counted in `dropped`) when flag 1 is not set, x, y or z is not finite, or a voxel
+ *                      index is outside -2^20 .. 2^20 - 1.  Per axis in fp64, one rounding per operation: t = (p - origin) / voxel,
+ *                      i = floor(t), q = (int)floor((t - i) * 65536).  The voxel (ix, iy, iz) accumulates n += 1, sum_q += q; with
+ *                      flag 2 and every |normal component| <= 2: n_normal += 1, sum_n += (int64)rint(normal * 32767); with flag 8:
+ *                      n_colour += 1, sum_rgb += rgb; with label == 1: n_glass += 1; first_seen / last_seen: the serials of the
+ *                      first and the last call that reached it.  Voxels are ranked by birth = (serial of the call that created
+ *                      them, their smallest row of that call): A then B gives the voxels and the order of A || B in one call.  A
+ *                      call that would bring count above max_voxels sets status 1 and changes nothing else; from then on the
+ *                      contents are undefined until gwd_scene_reset, and calls return at once on the device.  serial advances by one
+ *                      per call whatever happened (at most 2^31 - 1 calls and 2^31 - 1 observations per voxel are supported).
+ *                      Five launches (claim, count, scan, rank, add); 64-bit compare-and-swap, 64-bit min and integer adds only,
+ *                      so the result does not depend on scheduling; no thread waits for another, a probe visits at most `slots`
+ *                      slots; nothing is read back: serial, count and status live in `state`.
+ * gwd_scene_extract    cloud [max_voxels][32] uint8 and voxel_stats [max_voxels][4] int32 (n, n_glass, first_seen, last_seen), both
+ *                      16-byte aligned: one row per KEPT voxel in rank order - n >= min_obs (>= 1) and keep admits its label (1 when
+ *                      2 n_glass >= n, else 0; GWD_CLOUD_KEEP_*) - every row behind them zero; cloud_offsets [2] int32 = {0, kept}.
+ *                      position ((i + (sum_q / n + 0.5) / 65536) * voxel) + origin per axis in fp64, in that order, one rounding
+ *                      to fp32; normal sum_n / |sum_n| in fp64 (flag 2) when n_normal > 0 and the sum is not zero, else zeros; rgb
+ *                      (2 sum + n_colour) / (2 n_colour) in integers (flag 8), 0 without colour; region, source, frame 0; flags
+ *                      1 | GWD_SCENE_FLAG_MERGED | those.  With status != 0: all zero, cloud_offsets {0, 0}; never a truncated map.
+ *                      Three launches; the map is not changed.
+ * workspace: gwd_query_workspace(GWD_WS_SCENE, {rows, max_voxels}) bytes, 16-byte aligned, needs no initialisation.
+ * -1 on a null pointer or a size / range outside its limits, -2 on a keep outside its enum or a voxel / origin that is NaN, infinite
+ * or (voxel) not positive, -3 when a pointer is not aligned to its element (voxels, cloud, voxel_stats, workspace: 16 bytes);
+ * nothing is launched then.                                                                                                   */
+#define GWD_SCENE_TILE 1024
+#define GWD_SCENE_VOXEL_BYTES 128
+#define GWD_SCENE_MAX_VOXELS 134217728
+#define GWD_SCENE_FLAG_MERGED 16
+typedef struct gwd_scene_desc {
+    uint64_t *keys;
+    uint64_t *marks;
+    int32_t *ranks;
+    void *voxels;
+    int64_t *state;
+    double voxel;
+    double origin[3];
+    int64_t max_voxels, slots;
+} gwd_scene_desc;
+int gwd_scene_reset(const gwd_scene_desc *map, void *stream);
+int gwd_scene_integrate(const gwd_scene_desc *map, const uint8_t *cloud, const int32_t *cloud_offsets, int64_t rows, int32_t n_offsets,
+                        void *workspace, void *stream);
+int gwd_scene_extract(const gwd_scene_desc *map, int32_t min_obs, int32_t keep, void *workspace, uint8_t *cloud, int32_t *cloud_offsets,
+                      int32_t *voxel_stats, void *stream);
 
 #ifdef __cplusplus
 }
