@@ -7,6 +7,8 @@
 //   gwd_set_losses_backward  their gradients w.r.t. logits and lines.
 //   gwd_set_losses_focal_*   the same two launches with the label term of --label_loss_func focal_loss (SetCriterion.label_focal_loss,
 //                            /root/reference/src/models/glassrgbd.py:177-194): mean over the B*Q queries of w * nll * (1 - p_t)^gamma.
+//                            Here u = 1 - p_t is the sum of the other classes' probabilities and nll = -log p_t is -log1p(-u) where
+//                            u < 1/2 (focal_nll below): the log-sum-exp form loses a small nll to the rounding of s.
 // Targets arrive PADDED to a fixed capacity (criteria.PackedTargets): column t belongs to image bidx[t], valid[t] = 0 marks padding,
 // the LSAP hands padding columns the dummy query Q
 // (and, where an image has more targets than queries, its unmatched targets: they take no part in either term).  As torch ops this was ~40 launches forward and ~25 backward on a few KB of data.
@@ -35,6 +37,12 @@ __device__ __forceinline__ float others_prob(const float *lg, int K, int c, floa
         if (k != c) so += expf(lg[k] - mx);
     return so / s;
 }
+
+// -log p[c] of the focal kernels (lc = lg[c] - mx).  With c the largest class, -(lc - logf(s)) is logf(1 + so): the rounding of s is an
+// ABSOLUTE error of one fp32 unit there, a relative error 2^-24 / u of a small nll that u^(gamma-1) * nll carries into the whole row's
+// gradient.  u is a sum of positive terms, good to a few ulp however small: below 1/2 take -log1p(-u); above, both terms of the
+// difference are positive and the difference itself is fine
+__device__ __forceinline__ float focal_nll(float lc, float s, float u) { return u < 0.5f ? -log1pf(-u) : -(lc - logf(s)); }
 
 // u^g with torch.pow's conventions: u^0 = 1 also at u = 0
 __device__ __forceinline__ float focal_pow(float u, float g) { return g == 0.f ? 1.f : (g == 2.f ? u * u : powf(u, g)); }
@@ -92,11 +100,13 @@ __global__ __launch_bounds__(256) void set_losses_fwd_kernel(const float *__rest
         float s = 0.f;
         for (int k = 0; k < K; ++k) s += expf(lg[k] - mx);
         const int c = tcl[i];
-        const float nll = -((lg[c] - mx) - logf(s)), w = cls_w[c];
-        if (FOCAL)
-            s_n += (double)(nll * w * focal_pow(others_prob(lg, K, c, mx, s), gamma));
-        else
-            s_n += (double)(nll * w);
+        const float w = cls_w[c];
+        if (FOCAL) {
+            const float u = others_prob(lg, K, c, mx, s);
+            s_n += (double)(focal_nll(lg[c] - mx, s, u) * w * focal_pow(u, gamma));
+        } else {
+            s_n += (double)(-((lg[c] - mx) - logf(s)) * w);
+        }
         s_w += (double)w;
     }
     red[0][tid] = s_n;
@@ -120,7 +130,8 @@ __global__ __launch_bounds__(256) void set_losses_fwd_kernel(const float *__rest
 }
 
 // dlogits fully written; dlines must be zero on entry (matched rows are added).  FOCAL: d ce / d logits[k] =
-// w / (B*Q) * (p_k - [k = c]) * (u^gamma + gamma * u^(gamma-1) * p_t * nll), the second term absent for gamma = 0
+// w / (B*Q) * (p_k - [k = c]) * (u^gamma + gamma * u^(gamma-1) * p_t * nll), the second term absent for gamma = 0; nll from focal_nll,
+// as in the forward kernel
 template <bool FOCAL>
 __global__ __launch_bounds__(256) void set_losses_bwd_kernel(const float *__restrict__ logits, const float *__restrict__ lines,
                                                              const float *__restrict__ tl, const int32_t *__restrict__ bidx,
@@ -144,7 +155,7 @@ __global__ __launch_bounds__(256) void set_losses_bwd_kernel(const float *__rest
             for (int k = 1; k < K; ++k) mx = fmaxf(mx, lg[k]);
             float s = 0.f;
             for (int k = 0; k < K; ++k) s += expf(lg[k] - mx);
-            const float nll = -((lg[c] - mx) - logf(s)), u = others_prob(lg, K, c, mx, s);
+            const float u = others_prob(lg, K, c, mx, s), nll = focal_nll(lg[c] - mx, s, u);
             float m = focal_pow(u, gamma);
             // u = 0 means nll = 0: for gamma < 1 the limit of u^(gamma-1) * nll is 0, the product would be inf * 0
             if (gamma != 0.f && (u > 0.f || gamma >= 1.f)) m += gamma * focal_pow(u, gamma - 1.f) * p[c] * nll;

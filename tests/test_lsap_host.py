@@ -1,39 +1,18 @@
-"""csrc/lsap.hip compiled for the CPU (tests/lsap_host.cpp: the kernel's own source, one thread per lane, barriers and shuffles
-emulated): the matrices no GPU test feeds the kernel.  Finite costs give scipy's assignment in both orientations and both workgroup
+"""csrc/lsap.hip compiled for the CPU (tests/lsap_host.cpp: the kernel's own source, one fiber per lane, barriers and shuffles
+emulated; built by tests/lsap_build.py): the matrices no GPU test feeds the kernel.  Finite costs give scipy's assignment in both orientations and both workgroup
 sizes; NaN, +inf, -inf and all-NaN matrices end within the barrier count that the kernel's loop bounds allow and return a valid
 matching (distinct pairs, min(Q, T) of them) - arbitrary, not optimal, once a non-finite cost has been read as 1e30."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 from scipy.optimize import linear_sum_assignment
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from tests import lsap_build
+from tests.lsap_build import solve
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("lsap") / "liblsap_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I", os.path.join(ROOT, "gw_depth_amd", "csrc"),
-                           os.path.join(HERE, "lsap_host.cpp"), "-o", out])
-    lib = ctypes.CDLL(out)
-    vp = ctypes.c_void_p
-    lib.lsap_host.argtypes = [vp, vp, vp] + [ctypes.c_int] * 5
-    lib.lsap_host.restype = ctypes.c_long
-    return lib
-
-
-def solve(lib, cost, sizes, pad, waves):
-    """cost (Q, sum(sizes) + pad) fp32, one layer, B = len(sizes) images sharing the cost rows -> (query of every column, barriers)."""
-    B, (Q, sumT) = len(sizes), cost.shape
-    c = np.ascontiguousarray(np.broadcast_to(cost, (1, B, Q, sumT)), np.float32)
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    out = np.full((1, sumT), -7, np.int32)
-    n = lib.lsap_host(c.ctypes.data, off.ctypes.data, out.ctypes.data, 1, B, Q, sumT, waves)
-    return out[0], off, n
+    return lsap_build.build(tmp_path_factory.mktemp("lsap"))
 
 
 def barrier_bound(Q, T, waves):
