@@ -3,7 +3,8 @@
 A cloud is a (capacity, 32) uint8 tensor: float32 x y z nx ny nz, then uint8 red green blue label region source frame flags
 (include/gwdepth.h, gwd_point_cloud).  fields() names the columns without copying; save_ply writes a binary PLY whose vertex element
 IS the record, so saving is a header, one copy to the host and one write.  SceneMap owns the device memory of
-a voxel map and issues gwd_scene_reset / gwd_scene_integrate / gwd_scene_extract on it."""
+a voxel map and issues gwd_scene_reset / gwd_scene_integrate / gwd_scene_extract on it; SceneMap.view looks at the map from posed cameras
+(gwd_cloud_view, section 33)."""
 import numpy as np
 import torch
 
@@ -147,6 +148,12 @@ class SceneMap:
                                          seen, zeros behind them - cloud_offsets (2,) int32 = [0, kept], voxel_stats (max_voxels, 4)
                                          int32 = n, n_glass, first_seen, last_seen; fields / save_ply / load_ply take the cloud as it
                                          is.  Three launches, no host sync; the map is unchanged.
+    m.view(intrinsics, sizes, poses=None, plane=None, min_obs=1, keep="all", footprint=None, **options)
+                                         the map seen from posed cameras: extract(min_obs, keep), then
+                                         ops.cloud_view of the extraction - footprint=None: the map's voxel; options: min_depth,
+                                         max_depth, max_splat - -> ops.VIEW_KEYS (view_depth, view_labels, view_index, view_rgb at
+                                         frame size) + SCENE_KEYS, so view_index leads into voxel_stats.  Six launches, no host
+                                         sync; the map is unchanged; an overflowed map gives empty planes, never a partial picture.
     m.reset()                            an empty map again; one launch.
     m.state()                            ONE copy to the host (waits for the device; off the path): dict of serial, count, points,
                                          dropped, status.
@@ -191,6 +198,17 @@ class SceneMap:
                "voxel_stats": new((self.max_voxels, 4), torch.int32)}
         hip.library().scene_extract(self._desc, self._tensors, opt["min_obs"], opt["keep"], self._workspace(1), res["cloud"],
                                     res["cloud_offsets"], res["voxel_stats"])
+        return res
+
+    def view(self, intrinsics, sizes, poses=None, plane=None, min_obs=1, keep="all", footprint=None, view_sizes=None, **options):
+        from . import ops
+        if set(options) - {"min_depth", "max_depth", "max_splat"}:
+            raise TypeError("view: unknown option(s) %s (known: min_depth, max_depth, max_splat)" % sorted(set(options) - {"min_depth", "max_depth", "max_splat"}))
+        check_extract_options(min_obs, keep)
+        opt = ops.check_view_options(footprint=self.voxel if footprint is None else footprint, **options)      # before anything is launched
+        ext = self.extract(min_obs, keep)
+        res = ops.cloud_view(ext["cloud"], ext["cloud_offsets"], intrinsics, sizes, poses=poses, plane=plane, view_sizes=view_sizes, **opt)
+        res.update(ext)
         return res
 
     def state(self):

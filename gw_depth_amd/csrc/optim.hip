@@ -76,6 +76,7 @@ int64_t gwd_regions_workspace_bytes(int64_t B, int64_t Fh, int64_t Fw, int64_t m
 int64_t gwd_fusion_workspace_bytes(int64_t B, int64_t Fh, int64_t Fw);       // fusion.hip
 int64_t gwd_cloud_workspace_bytes(int64_t B, int64_t Fh, int64_t Fw, int64_t stride);               // cloud.hip
 int64_t gwd_scene_workspace_bytes(int64_t rows, int64_t max_voxels);       // scene.hip
+int64_t gwd_view_workspace_bytes(int64_t V, int64_t Fh, int64_t Fw);        // view.hip
 
 extern "C" int64_t gwd_query_workspace(int32_t op, const int64_t *dims, int32_t ndims) {
     if (!dims) return -1;
@@ -89,6 +90,7 @@ extern "C" int64_t gwd_query_workspace(int32_t op, const int64_t *dims, int32_t 
         case GWD_WS_FUSION: return ndims == 3 ? gwd_fusion_workspace_bytes(dims[0], dims[1], dims[2]) : -1;
         case GWD_WS_CLOUD: return ndims == 4 ? gwd_cloud_workspace_bytes(dims[0], dims[1], dims[2], dims[3]) : -1;
         case GWD_WS_SCENE: return ndims == 2 ? gwd_scene_workspace_bytes(dims[0], dims[1]) : -1;
+        case GWD_WS_VIEW: return ndims == 3 ? gwd_view_workspace_bytes(dims[0], dims[1], dims[2]) : -1;
         default: return -1;
     }
 }

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GWD_LIB") or os.path.join(_HERE, "libgwdepth_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3, 4
-WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS, WS_FUSION, WS_CLOUD, WS_SCENE = 0, 1, 2, 3, 4, 5, 6, 7, 8          # gwd_query_workspace ops
+WS_INORM_GELU, WS_RESAMPLE_BWD, WS_EVAL, WS_PLANE, WS_HEALTH, WS_REGIONS, WS_FUSION, WS_CLOUD, WS_SCENE, WS_VIEW = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9          # gwd_query_workspace ops
 GATHER_CONV, GATHER_TRANSPOSED, GATHER_UPSAMPLED = 0, 1, 2
 RESAMPLE_BILINEAR_AC, RESAMPLE_NEAREST = 0, 1
 
@@ -49,6 +49,7 @@ ENTRY_POINTS = [
     "gwd_render_frames",
     "gwd_point_cloud",
     "gwd_scene_reset", "gwd_scene_integrate", "gwd_scene_extract",
+    "gwd_cloud_view",
 ]
 
 
@@ -152,6 +153,9 @@ SCENE_VOXEL_BYTES = 128   # GWD_SCENE_VOXEL_BYTES: the accumulators of one voxel
 SCENE_MAX_VOXELS = 1 << 27    # GWD_SCENE_MAX_VOXELS
 SCENE_FLAG_MERGED = 16    # GWD_SCENE_FLAG_MERGED
 SCENE_STATE = ("serial", "count", "points", "dropped", "status")      # the first five int64 of gwd_scene_desc.state
+VIEW_TILE = 1024          # GWD_VIEW_TILE: rows of the cloud per workgroup of gwd_cloud_view's splat launch
+VIEW_MAX_SPLAT = 64       # GWD_VIEW_MAX_SPLAT: the widest square a row is drawn as, pixels
+VIEW_MAX_VIEWS = 16       # cameras per call of gwd_cloud_view
 GATHER_BATCH = 48         # gwd_gather2d_batch jobs: RGB, depth and labels of AUGMENT_BATCH frames
 COLOR_ADJUST, COLOR_SUMS = 0, 1
 
@@ -191,6 +195,15 @@ class SceneDesc(ctypes.Structure):
     """gwd_scene_desc (include/gwdepth.h)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("keys", "marks", "ranks", "voxels", "state")] + \
                [("voxel", ctypes.c_double), ("origin", ctypes.c_double * 3), ("max_voxels", ctypes.c_int64), ("slots", ctypes.c_int64)]
+
+
+class ViewDesc(ctypes.Structure):
+    """gwd_view_desc (include/gwdepth.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("cloud", "cloud_offsets", "sizes", "intrinsics", "poses", "workspace", "view_depth",
+                                               "view_index", "view_labels", "view_rgb")] + \
+               [(n, ctypes.c_double) for n in ("min_depth", "max_depth", "footprint")] + [("rows", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("n_offsets", "V", "Fh", "Fw", "max_splat", "keep")] + \
+               [("ext_h", ctypes.c_int32 * 16), ("ext_w", ctypes.c_int32 * 16)]
 
 
 class ResampleJob(ctypes.Structure):
@@ -385,6 +398,7 @@ class HipLibrary:
         L.gwd_scene_reset.argtypes = [ctypes.POINTER(SceneDesc), vp]
         L.gwd_scene_integrate.argtypes = [ctypes.POINTER(SceneDesc), vp, vp, i64, i32, vp, vp]
         L.gwd_scene_extract.argtypes = [ctypes.POINTER(SceneDesc), i32, i32, vp, vp, vp, vp, vp]
+        L.gwd_cloud_view.argtypes = [ctypes.POINTER(ViewDesc), vp]
 
     # ------------------------------------------------------------------ plumbing
     @staticmethod
@@ -1678,6 +1692,60 @@ class HipLibrary:
         self._check(self.lib.gwd_scene_extract(ctypes.byref(desc), int(min_obs), CLOUD_KEEP[keep], _ptr(workspace), _ptr(cloud),
                                                _ptr(cloud_offsets), _ptr(voxel_stats),
                                                self._stream(workspace, cloud, cloud_offsets, voxel_stats, *tensors)), "gwd_scene_extract")
+
+    @staticmethod
+    def view_desc(cloud, cloud_offsets, sizes, intrinsics, poses, view_sizes, min_depth, max_depth, footprint, max_splat, keep, workspace,
+                  view_depth, view_index, view_labels, view_rgb):
+        """The gwd_view_desc of a call (no device work).  ext = what the host knows of every view: the plane and view_sizes (None, or V
+        (fh, fw) pairs).  Raises on a dtype, a layout, a size or an option the kernels do not take."""
+        HipLibrary.scene_cloud_check("gwd_cloud_view", cloud, cloud_offsets)
+        HipLibrary._typed("gwd_cloud_view", ((sizes, torch.int32), (intrinsics, torch.float64), (poses, torch.float64),
+                                             (workspace, torch.uint8), (view_depth, torch.float32), (view_index, torch.int32),
+                                             (view_labels, torch.uint8), (view_rgb, torch.uint8)))
+        if any(t is None for t in (sizes, intrinsics, workspace, view_depth, view_index, view_labels, view_rgb)) or view_depth.dim() != 3:
+            raise ValueError("gwd_cloud_view: view_depth must be (V, Fh, Fw), and only poses may be None")
+        V, Fh, Fw = view_depth.shape
+        shape = (V, Fh, Fw)
+        if not 1 <= V <= VIEW_MAX_VIEWS or not 1 <= Fh <= 16384 or not 1 <= Fw <= 16384 or tuple(view_index.shape) != shape \
+                or tuple(view_labels.shape) != shape or tuple(view_rgb.shape) != shape + (3,) or tuple(sizes.shape) != (V, 2) \
+                or tuple(intrinsics.shape) != (V, 4) or (poses is not None and tuple(poses.shape) != (V, 3, 4)) \
+                or (view_sizes is not None and len(view_sizes) != V) or not 1 <= cloud.shape[0] <= 2 ** 31 - 1 or cloud_offsets.numel() < 2:
+            raise ValueError("gwd_cloud_view: operand sizes do not match (V, Fh, Fw) = (%d, %d, %d), V <= %d, sides <= 16384, 1 <= rows "
+                             "<= 2^31 - 1, at least two offsets" % (shape + (VIEW_MAX_VIEWS,)))
+        if any(t is not None and not t.is_contiguous() for t in (sizes, intrinsics, poses, workspace, view_depth, view_index, view_labels,
+                                                                 view_rgb)):
+            raise ValueError("gwd_cloud_view: every operand is contiguous")
+        if isinstance(max_splat, bool) or int(max_splat) != max_splat or not 1 <= int(max_splat) <= VIEW_MAX_SPLAT or keep not in CLOUD_KEEP:
+            raise ValueError("gwd_cloud_view: 1 <= max_splat <= %d and keep one of %s, got %r, %r" % (VIEW_MAX_SPLAT, sorted(CLOUD_KEEP), max_splat, keep))
+        min_depth, max_depth, footprint = float(min_depth), float(max_depth), float(footprint)
+        if not 0.0 < min_depth <= max_depth < float("inf") or not 0.0 <= footprint < float("inf"):
+            raise ValueError("gwd_cloud_view: 0 < min_depth <= max_depth and footprint >= 0, all finite; got %r, %r, %r" % (min_depth, max_depth, footprint))
+        d = ViewDesc()
+        for n, t in (("cloud", cloud), ("cloud_offsets", cloud_offsets), ("sizes", sizes), ("intrinsics", intrinsics), ("poses", poses),
+                     ("workspace", workspace), ("view_depth", view_depth), ("view_index", view_index), ("view_labels", view_labels),
+                     ("view_rgb", view_rgb)):
+            setattr(d, n, None if t is None else _ptr(t).value)
+        d.min_depth, d.max_depth, d.footprint = min_depth, max_depth, footprint
+        d.rows, d.n_offsets, d.V, d.Fh, d.Fw, d.max_splat, d.keep = cloud.shape[0], cloud_offsets.numel(), V, Fh, Fw, int(max_splat), CLOUD_KEEP[keep]
+        for v in range(V):
+            h, w = (Fh, Fw) if view_sizes is None else (min(int(view_sizes[v][0]), Fh), min(int(view_sizes[v][1]), Fw))
+            if h < 1 or w < 1:
+                raise ValueError("gwd_cloud_view: view %d is empty (%d x %d)" % (v, h, w))
+            d.ext_h[v], d.ext_w[v] = h, w
+        return d
+
+    def cloud_view(self, cloud, cloud_offsets, sizes, intrinsics, poses, view_sizes, min_depth, max_depth, footprint, max_splat, keep,
+                   workspace, view_depth, view_index, view_labels, view_rgb):
+        """gwd_cloud_view: view_depth float32 / view_index int32 / view_labels uint8 (V,Fh,Fw) and view_rgb uint8 (V,Fh,Fw,3) out, every
+        byte written.  cloud (rows >= 1, 32) uint8 with cloud_offsets (>= 2,) int32, sizes (V,2) int32, intrinsics (V,4) float64, poses
+        (V,3,4) float64 camera-to-world or None; view_sizes: None or what the host knows of sizes; keep a key of CLOUD_KEEP; workspace:
+        a uint8 tensor of workspace_bytes(WS_VIEW, V, Fh, Fw) bytes."""
+        d = self.view_desc(cloud, cloud_offsets, sizes, intrinsics, poses, view_sizes, min_depth, max_depth, footprint, max_splat, keep,
+                           workspace, view_depth, view_index, view_labels, view_rgb)
+        if workspace.numel() < self.workspace_bytes(WS_VIEW, d.V, d.Fh, d.Fw):
+            raise ValueError("gwd_cloud_view: the workspace is smaller than workspace_bytes(WS_VIEW, V, Fh, Fw)")
+        every = (cloud, cloud_offsets, sizes, intrinsics, poses, workspace, view_depth, view_index, view_labels, view_rgb)
+        self._check(self.lib.gwd_cloud_view(ctypes.byref(d), self._stream(*every)), "gwd_cloud_view")
 
 
 _LIB = None

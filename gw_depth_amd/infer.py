@@ -34,6 +34,9 @@ _CLOUD_OPTIONS = ("stride", "edge", "normals", "keep", "depth", "min_depth", "ma
 _CLOUD_DEPTHS = ("auto", "depth", "depth_planar", "depth_fused")
 CLOUD_KEYS = ops.CLOUD_KEYS                                            # ... with cloud=, by a call that passes intrinsics=
 _SCENE_OPTIONS = ("voxel", "max_voxels", "origin", "slots")
+_SCENE_VIEW_OPTIONS = ("min_obs", "keep", "footprint", "max_splat")
+SCENE_VIEW_KEYS = ("scene_depth", "scene_labels", "scene_index", "scene_rgb", "scene_cloud", "scene_cloud_offsets", "scene_stats")      # ... with scene_view=
+_SCENE_VIEW_SOURCE = ("view_depth", "view_labels", "view_index", "view_rgb", "cloud", "cloud_offsets", "voxel_stats")
 
 
 class InferenceSession:
@@ -122,12 +125,21 @@ class InferenceSession:
     gives the merged map whenever it is wanted.  A call with intrinsics but without poses raises: camera-frame clouds share no world.
     A call without intrinsics returns what it returns today and leaves the map alone.  predict() does not take part.
 
+    SCENE VIEW.  scene_view=None (the default): nothing is allocated, launched or returned that is not there without it.  scene_view=True
+    or a dict (min_obs, keep, footprint - None: the map's voxel - max_splat) needs scene=: predict_frames(intrinsics=..., poses=...)
+    first looks at sess.scene from the call's own cameras - its intrinsics, poses and frame sizes, the session's min_depth / max_depth,
+    the result planes' Fh x Fw - BEFORE this call's cloud is integrated (SceneMap.view: six launches, gwd_scene_extract +
+    gwd_cloud_view, no host sync) and adds SCENE_VIEW_KEYS: scene_depth / scene_labels / scene_index / scene_rgb - what the earlier
+    calls said about every pixel of these frames (0 / 255 / -1 / 0 where they said nothing; all of it on the first call) - and
+    scene_cloud / scene_cloud_offsets / scene_stats, the extraction scene_index points into.  A call without intrinsics returns what
+    it returns today.  predict() does not take part.
+
     A ragged batch is top-left aligned (nested_tensor_from_tensor_list), so the un-padded (h, w) of each image are counted
     from the pad mask on the device; padding comes out as depth 0 / millimetres 0 / label 255."""
 
     def __init__(self, model, compute_dtype=torch.bfloat16, graph=True, min_depth=1e-3, max_depth=10.0, score_thresh=0.6,
                  line_nms=None, line_nms_order="score", line_nms_min_score=None, regions=None, line_profiles=None, fusion=None,
-                 render=None, cloud=None, scene=None):
+                 render=None, cloud=None, scene=None, scene_view=None):
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("compute_dtype must be torch.float32 or torch.bfloat16")
         if line_nms_order not in ("score", "query"):
@@ -165,6 +177,7 @@ class InferenceSession:
         self.render = self._check_render(render)
         self.cloud = self._check_cloud(cloud)
         self.scene = self._check_scene(scene)
+        self.scene_view = self._check_scene_view(scene_view)
         self._cache = graphs.GraphCache()                  # every signature is captured at its first sight
         self._graphs = self._cache.entries                 # signature -> {"graph": chain of one, or None, ...}, least recently used first
         self._side = graphs.GraphSide()
@@ -523,6 +536,25 @@ class InferenceSession:
             plane[k, :h, :w].copy_(InferenceSession._upload_frame(t, device), non_blocking=True)
         return plane
 
+    def _check_scene_view(self, scene_view):
+        """scene_view= -> None or SceneMap.view's options as a dict."""
+        if scene_view is None:
+            return None
+        if scene_view is not True and not isinstance(scene_view, dict):
+            raise TypeError("scene_view must be None, True or a dict of %s, got %r" % (", ".join(_SCENE_VIEW_OPTIONS), scene_view))
+        if self.scene is None:
+            raise ValueError("scene_view= needs a session built with scene= (it is the map that is looked at)")
+        given = scene_view if isinstance(scene_view, dict) else {}
+        if set(given) - set(_SCENE_VIEW_OPTIONS):
+            raise TypeError("scene_view: unknown option(s) %s (known: %s)" % (sorted(set(given) - set(_SCENE_VIEW_OPTIONS)), ", ".join(_SCENE_VIEW_OPTIONS)))
+        from . import cloud as PC
+        opt = dict(given)
+        footprint = opt.pop("footprint", None)
+        extract = PC.check_extract_options(opt.pop("min_obs", 1), opt.pop("keep", "all"))
+        view = ops.check_view_options(min_depth=self.min_depth, max_depth=self.max_depth,
+                                      footprint=self.scene.voxel if footprint is None else footprint, keep=extract["keep"], **opt)
+        return dict(min_obs=extract["min_obs"], keep=extract["keep"], footprint=footprint, max_splat=view["max_splat"])
+
     def predict_frames(self, frames, size=1024, max_size=1024, ensemble=False, pad_to=None, copy=False, intrinsics=None,
                        sensor_depth=None, poses=None):
         """Decoded camera frames in, results at each frame's own size out.  frames: list of uint8 (h,w,3) tensors, host or device,
@@ -628,6 +660,10 @@ class InferenceSession:
         if self.cloud is not None and intrinsics is not None:      # behind fusion and profiles, before render; the frames are read where they lie
             with torch.no_grad(), self._on_stream():
                 res.update(self._cloud(on_dev[:B], frame_sizes, res, intrinsics, poses))
+                if self.scene_view is not None:            # what the earlier calls said about these frames: before this call's cloud goes in
+                    seen = self.scene.view(intrinsics, fsz, poses=poses, plane=tuple(depth.shape[1:]), view_sizes=frame_sizes,
+                                           min_depth=self.min_depth, max_depth=self.max_depth, **self.scene_view)
+                    res.update({k: seen[src] for k, src in zip(SCENE_VIEW_KEYS, _SCENE_VIEW_SOURCE)})
                 if self.scene is not None:                 # behind the cloud, before render; the map is the session's, not the call's
                     self.scene.integrate(res["cloud"], res["cloud_offsets"])
         if self.render is not None:                        # behind everything else, on the same stream; the uploaded frames are read where they are

@@ -2564,3 +2564,101 @@ def scene_merge(cloud, cloud_offsets, voxel, max_voxels=None, origin=(0.0, 0.0, 
     _cloud.check_integrate_operands(cloud, cloud_offsets)
     m = _cloud.SceneMap(opt["voxel"], opt["max_voxels"], opt["origin"], opt["slots"], device=cloud.device)
     return m.integrate(cloud, cloud_offsets).extract(opt["min_obs"], opt["keep"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------- scene view
+VIEW_KEYS = ("view_depth", "view_labels", "view_index", "view_rgb")
+
+
+def check_view_options(min_depth=1e-3, max_depth=10.0, footprint=0.0, max_splat=32, keep="all"):
+    """Host validation of cloud_view's options; -> them as a dict."""
+    for name, value in (("min_depth", min_depth), ("max_depth", max_depth), ("footprint", footprint)):
+        try:
+            if isinstance(value, (bool, str)):
+                raise TypeError
+            float(value)
+        except (TypeError, ValueError):
+            raise TypeError("cloud_view: %s must be a number of metres, got %r" % (name, value))
+    if not 0.0 < float(min_depth) <= float(max_depth) < float("inf"):
+        raise ValueError("cloud_view: 0 < min_depth <= max_depth, both finite, got %r, %r" % (min_depth, max_depth))
+    if not 0.0 <= float(footprint) < float("inf"):
+        raise ValueError("cloud_view: footprint must be finite and >= 0 metres, got %r" % (footprint,))
+    max_splat = _whole("max_splat", max_splat, "cloud_view")
+    if not 1 <= max_splat <= hip.VIEW_MAX_SPLAT:
+        raise ValueError("cloud_view: 1 <= max_splat <= %d pixels, got %r" % (hip.VIEW_MAX_SPLAT, max_splat))
+    if keep not in hip.CLOUD_KEEP:
+        raise ValueError("cloud_view: keep must be one of %s, got %r" % (", ".join(repr(k) for k in hip.CLOUD_KEEP), keep))
+    return dict(min_depth=float(min_depth), max_depth=float(max_depth), footprint=float(footprint), max_splat=max_splat, keep=keep)
+
+
+def cloud_view(cloud, cloud_offsets, intrinsics, sizes, poses=None, plane=None, view_sizes=None, **options):
+    """A cloud seen from V <= 16 posed pinhole cameras, z-buffered on the device (gwd_cloud_view, DESIGN.md section 33;
+    tests/view_ref.py is the statement): cloud (rows, 32) uint8 with cloud_offsets int32 (only its last entry, the total, is read) -
+    point_cloud's, or SceneMap.extract's - intrinsics (V,4) (fx, fy, cx, cy), sizes (V,2) (fh, fw), poses (V,3,4) camera-to-world rows
+    [R | t] as point_cloud takes them (None: the cloud is in the camera's frame).  intrinsics and poses: tensors or nested sequences,
+    taken as float64.  sizes: a nested sequence, or an int32 tensor on the cloud's device - then plane = (Fh, Fw)
+    is needed, nothing is read back (view_sizes: what the host knows of such sizes, V pairs the device's are clamped to).  plane
+    defaults to the largest fh and fw.
+
+    A row with flag 1, finite coordinates and a label keep admits is drawn where min_depth <= Z <= max_depth as a square of
+    footprint metres (at least one pixel, at most max_splat pixels) around its projection; footprint=0: the one nearest pixel.  A
+    pixel keeps the nearest row (depth rounded once to float32, ties to the lowest row): exact, and the same bytes on every call.
+    -> dict in VIEW_KEYS order, fresh tensors: view_depth (V,Fh,Fw) float32 (0: empty), view_labels uint8 (255: empty), view_index
+    int32 (the row of the cloud, -1: empty), view_rgb (V,Fh,Fw,3) uint8 (0 without colour).  Three launches, no host sync."""
+    opt = check_view_options(**options)
+    if not torch.is_tensor(cloud) or cloud.dtype != torch.uint8 or cloud.dim() != 2 or cloud.shape[1] != hip.CLOUD_RECORD:
+        raise TypeError("cloud_view: cloud must be a (rows, %d) uint8 tensor" % hip.CLOUD_RECORD)
+    if not torch.is_tensor(cloud_offsets) or cloud_offsets.dtype != torch.int32:
+        raise TypeError("cloud_view: cloud_offsets must be an int32 tensor (point_cloud's, on the device)")
+    if cloud_offsets.dim() != 1 or cloud_offsets.numel() < 2 or cloud_offsets.device != cloud.device:
+        raise ValueError("cloud_view: cloud_offsets must be (B + 1,) on the cloud's device, got %s on %s" % (tuple(cloud_offsets.shape), cloud_offsets.device))
+    if cloud.shape[0] > 2 ** 31 - 1:
+        raise ValueError("cloud_view: at most 2^31 - 1 rows per call, got %d" % cloud.shape[0])
+    dev = cloud.device
+    intrinsics = torch.as_tensor(intrinsics, dtype=torch.float64)
+    if intrinsics.dim() != 2 or intrinsics.shape[1] != 4 or not 1 <= intrinsics.shape[0] <= hip.VIEW_MAX_VIEWS:
+        raise ValueError("cloud_view: intrinsics must be (V, 4) = (fx, fy, cx, cy) per view, 1 <= V <= %d, got %s" % (hip.VIEW_MAX_VIEWS, tuple(intrinsics.shape)))
+    V = intrinsics.shape[0]
+    if poses is not None:
+        poses = torch.as_tensor(poses, dtype=torch.float64)
+        if tuple(poses.shape) != (V, 3, 4):
+            raise ValueError("cloud_view: poses must be (%d, 3, 4) = rows [R | t] per view, got %s" % (V, tuple(poses.shape)))
+    on_device = torch.is_tensor(sizes) and sizes.device == dev
+    if torch.is_tensor(sizes) and sizes.dtype != torch.int32:
+        raise TypeError("cloud_view: sizes as a tensor must be int32")
+    if on_device:
+        if plane is None:
+            raise ValueError("cloud_view: sizes on the device need plane=(Fh, Fw): nothing is read back")
+    else:
+        view_sizes = sizes.tolist() if torch.is_tensor(sizes) else sizes
+    if view_sizes is not None:
+        try:
+            view_sizes = [(_whole("fh", h, "cloud_view"), _whole("fw", w, "cloud_view")) for h, w in view_sizes]
+        except ValueError:
+            raise ValueError("cloud_view: sizes is %d pairs (fh, fw)" % V)
+        if len(view_sizes) != V or any(h < 1 or w < 1 for h, w in view_sizes):
+            raise ValueError("cloud_view: sizes is %d pairs (fh, fw) >= 1, got %r" % (V, view_sizes))
+    if not on_device:
+        sizes = torch.tensor(view_sizes, dtype=torch.int32)
+    if tuple(sizes.shape) != (V, 2):
+        raise ValueError("cloud_view: sizes must be (%d, 2), got %s" % (V, tuple(sizes.shape)))
+    if plane is None:
+        plane = (max(h for h, _ in view_sizes), max(w for _, w in view_sizes))
+    try:
+        Fh, Fw = (_whole("plane", v, "cloud_view") for v in plane)
+    except ValueError:
+        raise ValueError("cloud_view: plane is (Fh, Fw), got %r" % (plane,))
+    if not 1 <= Fh <= 16384 or not 1 <= Fw <= 16384:
+        raise ValueError("cloud_view: a plane is 1 .. 16384 per side, got %r" % ((Fh, Fw),))
+    lib = _lib()
+    if cloud.shape[0] == 0:                               # no rows: one row without flag 1 stands in, the total is clamped anyway
+        cloud = torch.zeros((1, hip.CLOUD_RECORD), dtype=torch.uint8, device=dev)
+    to = lambda t: None if t is None else t.to(dev, non_blocking=True).contiguous()
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    ws = new((lib.workspace_bytes(hip.WS_VIEW, V, Fh, Fw),), torch.uint8)
+    res = {"view_depth": new((V, Fh, Fw), torch.float32), "view_labels": new((V, Fh, Fw), torch.uint8),
+           "view_index": new((V, Fh, Fw), torch.int32), "view_rgb": new((V, Fh, Fw, 3), torch.uint8)}
+    lib.cloud_view(cloud.contiguous(), cloud_offsets.contiguous(), to(sizes), to(intrinsics), to(poses), view_sizes, opt["min_depth"],
+                   opt["max_depth"], opt["footprint"], opt["max_splat"], opt["keep"], ws, res["view_depth"], res["view_index"],
+                   res["view_labels"], res["view_rgb"])
+    return res

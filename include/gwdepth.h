@@ -92,9 +92,10 @@ const char *gwd_arch(void);
  *   GWD_WS_FUSION          dims = {B, Fh, Fw}      -> `workspace` of gwd_fusion_ring / gwd_fusion_planes
  *   GWD_WS_CLOUD           dims = {B, Fh, Fw, stride} -> `workspace` of gwd_point_cloud
  *   GWD_WS_SCENE           dims = {rows, max_voxels} -> `workspace` of gwd_scene_integrate (a cloud of `rows` rows) / gwd_scene_extract
+ *   GWD_WS_VIEW            dims = {V, Fh, Fw}      -> `workspace` of gwd_cloud_view (the z-buffer)
  * Returns -1 for an unknown op or a wrong dimension count.                                                     */
 enum { GWD_WS_INORM_GELU = 0, GWD_WS_RESAMPLE_BWD = 1, GWD_WS_EVAL = 2, GWD_WS_PLANE = 3, GWD_WS_HEALTH = 4, GWD_WS_REGIONS = 5,
-       GWD_WS_FUSION = 6, GWD_WS_CLOUD = 7, GWD_WS_SCENE = 8 };
+       GWD_WS_FUSION = 6, GWD_WS_CLOUD = 7, GWD_WS_SCENE = 8, GWD_WS_VIEW = 9 };
 int64_t gwd_query_workspace(int32_t op, const int64_t *dims, int32_t ndims);
 
 /* Implicit-GEMM convolution on MFMA with fused epilogue y = act(scale*conv(x,w) + shift + residual).
@@ -1247,6 +1248,50 @@ int gwd_scene_integrate(const gwd_scene_desc *map, const uint8_t *cloud, const i
                         void *workspace, void *stream);
 int gwd_scene_extract(const gwd_scene_desc *map, int32_t min_obs, int32_t keep, void *workspace, uint8_t *cloud, int32_t *cloud_offsets,
                       int32_t *voxel_stats, void *stream);
+
+/* Scene view (csrc/view.hip): a cloud of 32-byte records - gwd_point_cloud's or gwd_scene_extract's - projected
+ * into V <= 16 posed pinhole cameras and z-buffered; tests/view_ref.py states the same in numpy.  cloud [rows][32] uint8 (16-byte
+ * aligned), cloud_offsets [n_offsets] int32 on the DEVICE, n_offsets >= 2: only its last entry, the total, is read (clamped to
+ * 0 .. rows); 1 <= rows <= 2^31 - 1.  sizes [V][2] int32 (fh, fw) on the DEVICE, intrinsics [V][4] fp64 (fx, fy, cx, cy), poses
+ * [V][3][4] fp64 camera-to-world rows [R | t] as gwd_point_cloud takes them (the view applies the transpose) or NULL: the cloud is in
+ * the camera's frame.  ext_h / ext_w [V]: what the HOST knows view v cannot exceed (1 .. Fh, 1 .. Fw): sizes is clamped to it, so
+ * nothing is written outside a plane whatever sizes holds.  Fh, Fw <= 16384.
+ *   a row r < total is drawn into view v unless flag 1 is clear, a coordinate is not finite or keep (GWD_CLOUD_KEEP_*: label == 1 /
+ *   label != 1) does not admit its label.  fp64, one rounding per operation: d = p - t, X = (r00 d0 + r10 d1) + r20 d2, Y and Z
+ *   likewise with the second and third column; min_depth <= Z <= max_depth; u = (fx X) / Z + cx, v = (fy Y) / Z + cy;
+ *   hx = max(0.5, min(max_splat / 2, ((0.5 footprint) fx) / Z)), hy with fy; the pixels ceil(u - hx) <= x <= ceil(u + hx) - 1 and
+ *   the same in y, clamped in fp64 to the frame (pixel centres are integers; footprint 0: the one nearest pixel, ties to the larger
+ *   coordinate); a NaN draws nothing.  A pixel keeps the smallest key float32(Z) bits << 32 | r drawn on it: the nearest point after
+ *   one rounding to fp32, ties to the lowest row.
+ * view_depth [V][Fh][Fw] fp32 (that float32, or 0), view_index [V][Fh][Fw] int32 (the row, or -1), both 16-byte aligned; view_labels
+ * [V][Fh][Fw] uint8 (the row's label, or 255), view_rgb [V][Fh][Fw][3] uint8 (the row's colour with flag 8, else 0), both 4-byte
+ * aligned: every byte is written, the pixels outside (fh, fw) hold the empty values.  workspace: gwd_query_workspace(GWD_WS_VIEW,
+ * {V, Fh, Fw}) bytes - the z-buffer, 8 per pixel - 16-byte aligned, needs no initialisation.  Three launches (clear, splat, resolve):
+ * one 64-bit unsigned min per covered pixel, skipped after a plain load when the stored key is smaller already; rectangles above 16
+ * pixels are walked by the whole wave.  No memset, no host synchronisation, no thread waits for another; the minimum is unique, so
+ * results are bit-identical from call to call.
+ * -1 on a null pointer or a size / range outside its limits, -2 on a keep outside its enum, max_splat outside 1 ..
+ * GWD_VIEW_MAX_SPLAT, a footprint that is NaN, negative or infinite, or depth bounds that are NaN or not 0 < min_depth <= max_depth <
+ * infinity, -3 when a pointer is not aligned as above; nothing is launched then.                                               */
+#define GWD_VIEW_TILE 1024
+#define GWD_VIEW_MAX_SPLAT 64
+typedef struct gwd_view_desc {
+    const uint8_t *cloud;
+    const int32_t *cloud_offsets;
+    const int32_t *sizes;
+    const double *intrinsics;
+    const double *poses;
+    void *workspace;
+    float *view_depth;
+    int32_t *view_index;
+    uint8_t *view_labels;
+    uint8_t *view_rgb;
+    double min_depth, max_depth, footprint;
+    int64_t rows;
+    int32_t n_offsets, V, Fh, Fw, max_splat, keep;
+    int32_t ext_h[16], ext_w[16];
+} gwd_view_desc;
+int gwd_cloud_view(const gwd_view_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }
