@@ -57,11 +57,6 @@ __global__ void gather2d_kernel(const uint8_t *__restrict__ src, uint8_t *__rest
     }
 }
 
-inline int flat_grid(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
 // ---- grouped forms: the passes of a whole BATCH of frames in one launch each.  The job records travel by value in the kernel
 // arguments (as gwd_colsum_batch's do), a workgroup finds its job through the block0 prefix, and every job's tables sit at int32
 // offsets inside one device buffer the caller uploaded once.  One thread per output PIXEL: its C bytes share the bounds, the
@@ -226,7 +221,7 @@ extern "C" int gwd_resample_u8_pass(const uint8_t *src, uint8_t *dst, const int3
     if (!src || !dst || !bounds || !kk || ksize <= 0 || n_out <= 0 || other <= 0 || C <= 0 || (axis != 0 && axis != 1)) return -1;
     if ((step0 != 1 && step0 != -1) || (step1 != 1 && step1 != -1)) return -1;
     const int64_t total = (int64_t)n_out * other * C;
-    resample_u8_kernel<<<flat_grid(total), 256, 0, (hipStream_t)stream>>>(src, dst, bounds, kk, ksize, axis, n_out, other, C, src_row_stride, base0,
+    resample_u8_kernel<<<flat_grid(total, 8192), 256, 0, (hipStream_t)stream>>>(src, dst, bounds, kk, ksize, axis, n_out, other, C, src_row_stride, base0,
                                                                           step0, base1, step1);
     GWD_CHECK_LAUNCH();
     return 0;
@@ -236,7 +231,7 @@ extern "C" int gwd_gather2d(const void *src, void *dst, const int32_t *ytab, con
                             int64_t src_row_stride_bytes, int32_t elem_bytes, void *stream) {
     if (!src || !dst || !ytab || !xtab || oh <= 0 || ow <= 0) return -1;
     hipStream_t s = (hipStream_t)stream;
-    const int g = flat_grid((int64_t)oh * ow);
+    const int g = flat_grid((int64_t)oh * ow, 8192);
     const uint8_t *sp = (const uint8_t *)src;
     uint8_t *dp = (uint8_t *)dst;
     switch (elem_bytes) {

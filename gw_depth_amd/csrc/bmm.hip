@@ -24,9 +24,6 @@ struct Operand {
     int64_t sb0, sb1, ld;          // element strides of the two batch dims and of the outer matrix dim (the inner one is 1)
 };
 
-__device__ __forceinline__ f32x16 bmma(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 bmma(float a, float b, const f32x16 &c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
 // VEC consecutive elements starting at p[0], of which the first `n` (0..VEC) exist
 template <typename T, int VEC>
 __device__ __forceinline__ void load_vec(const T *p, int n, T (&out)[VEC]) {
@@ -106,10 +103,10 @@ __global__ __launch_bounds__(256) void bmm_kernel(Operand A, Operand B, void *c,
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
             for (int ks = 0; ks < BK / 16; ++ks)
-                acc = bmma(*(const bf16x8 *)(Ab + ks * 16 + fh * 8), *(const bf16x8 *)(Bb + ks * 16 + fh * 8), acc);
+                acc = mma(*(const bf16x8 *)(Ab + ks * 16 + fh * 8), *(const bf16x8 *)(Bb + ks * 16 + fh * 8), acc);
         } else {
 #pragma unroll
-            for (int ks = 0; ks < BK / 2; ++ks) acc = bmma(Ab[ks * 2 + fh], Bb[ks * 2 + fh], acc);
+            for (int ks = 0; ks < BK / 2; ++ks) acc = mma(Ab[ks * 2 + fh], Bb[ks * 2 + fh], acc);
         }
         if (s + 1 < steps) {
             store_tile<T, AKM>(As[cur ^ 1], LDK, tid, ra);

@@ -11,10 +11,11 @@
 //                       operand to keep in step), the lane's rank = the tile's offset + the counts of the waves and rounds before
 //                       it (LDS) + the set bits below it in its wave's ballot, the record, two 16-byte stores; the rows from the
 //                       total to the capacity are zeroed grid-stride by the same workgroups.
+// The count per tile, the scan and the rank inside a tile are compact.h's, shared with scene.hip.
 // A tile's offset is a function of the counts alone: no workgroup waits for another, no atomic takes part, no memset; repeated calls
 // are bit-identical and a frame's rows depend on neither its slot nor its neighbours nor Fh x Fw.
 // All geometry is fp64, one rounding per operation (no contraction), one final rounding to fp32.
-#include "common.h"
+#include "compact.h"
 
 // tests/cloud_ref.py rounds after every operation; hipcc would contract a * b + c
 #pragma clang fp contract(off)
@@ -24,7 +25,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kRounds = GWD_CLOUD_TILE / kThreads;        // candidates per lane
-constexpr int kScanThreads = 1024;
 constexpr int kMaxB = 16;
 static_assert(GWD_CLOUD_TILE % kThreads == 0, "a tile is whole rounds of the workgroup");
 
@@ -54,8 +54,8 @@ __device__ __forceinline__ Frame frame_of(const CloudArgs &a, int block) {
     f.b = 0;
     while (f.b + 1 < a.B && block >= a.block0[f.b + 1]) ++f.b;
     f.tile = block - a.block0[f.b];
-    f.fh = min(max(a.sizes[2 * f.b], 0), a.ext_h[f.b]);
-    f.fw = min(max(a.sizes[2 * f.b + 1], 0), a.ext_w[f.b]);
+    f.fh = frame_side(a.sizes[2 * f.b], a.ext_h[f.b]);
+    f.fw = frame_side(a.sizes[2 * f.b + 1], a.ext_w[f.b]);
     f.nw = (f.fw + a.s - 1) / a.s;
     f.ncand = (int64_t)((f.fh + a.s - 1) / a.s) * f.nw;
     return f;
@@ -210,41 +210,14 @@ __global__ __launch_bounds__(kThreads) void cloud_count_kernel(const CloudArgs a
         const bool ok = candidate(a, f, (int64_t)f.tile * GWD_CLOUD_TILE + j * kThreads + threadIdx.x, x, y) && is_point(a, f, D, L, x, y);
         n += __popcll(__ballot(ok));
     }
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) t += part[w];
-        a.ws[blockIdx.x] = t;
-    }
+    tile_sum<kWaves>(n, part, &a.ws[blockIdx.x]);
 }
 
-// one workgroup: thread t owns `chunk` consecutive tiles; their sums are scanned over the workgroup, then every thread rewrites its
-// own tiles as exclusive offsets
+// one workgroup: the tile counts become exclusive offsets in place, the total behind them
 __global__ __launch_bounds__(kScanThreads) void cloud_scan_kernel(const CloudArgs a) {
     __shared__ int sums[kScanThreads];
     const int t = threadIdx.x;
-    const int chunk = (a.tiles + kScanThreads - 1) / kScanThreads;
-    const int lo = min(t * chunk, a.tiles), hi = min(lo + chunk, a.tiles);
-    int mine = 0;
-    for (int k = lo; k < hi; ++k) mine += a.ws[k];
-    sums[t] = mine;
-    __syncthreads();
-    for (int o = 1; o < kScanThreads; o <<= 1) {          // inclusive, Hillis-Steele
-        const int v = t >= o ? sums[t - o] : 0;
-        __syncthreads();
-        sums[t] += v;
-        __syncthreads();
-    }
-    int run = sums[t] - mine;
-    for (int k = lo; k < hi; ++k) {
-        const int c = a.ws[k];
-        a.ws[k] = run;
-        run += c;
-    }
-    if (t == kScanThreads - 1) a.ws[a.tiles] = sums[t];
-    __syncthreads();
+    scan_tiles(a.ws, a.tiles, sums);
     if (t <= a.B) a.offsets[t] = a.ws[t < a.B ? a.block0[t] : a.tiles];
 }
 
@@ -253,37 +226,25 @@ __global__ __launch_bounds__(kThreads) void cloud_emit_kernel(const CloudArgs a)
     const Frame f = frame_of(a, blockIdx.x);
     const float *__restrict__ D = a.depth + f.b * a.plane;
     const uint8_t *__restrict__ L = a.labels + f.b * a.plane;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int px[kRounds], py[kRounds], below[kRounds];
-    unsigned mine = 0u;
+    int px[kRounds], py[kRounds];
+    TileRank<kRounds, kWaves> points;
 #pragma unroll
     for (int j = 0; j < kRounds; ++j) {
         const bool ok = candidate(a, f, (int64_t)f.tile * GWD_CLOUD_TILE + j * kThreads + threadIdx.x, px[j], py[j]) &&
                         is_point(a, f, D, L, px[j], py[j]);
-        const unsigned long long m = __ballot(ok);
-        below[j] = __popcll(m & ((1ull << lane) - 1ull));
-        if (ok) mine |= 1u << j;
-        if (lane == 0) part[j * kWaves + wave] = __popcll(m);
+        points.vote(j, ok, part);
     }
     __syncthreads();
     const int64_t base = a.ws[blockIdx.x];
-    if (mine) {
+    if (points.any()) {
         Cam c;
         const double *cam = a.intrinsics + 4 * f.b;
         c.fx = cam[0], c.fy = cam[1], c.cx = cam[2], c.cy = cam[3];
-        int before = 0;                                   // the points of the rounds and waves ahead of this one
-#pragma unroll
-        for (int j = 0; j < kRounds; ++j) {
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                if (w == wave) below[j] += before;
-                before += part[j * kWaves + w];
-            }
-        }
+        points.finish(part);
 #pragma unroll
         for (int j = 0; j < kRounds; ++j) {               // a round's lanes store neighbouring rows
-            const int64_t row = base + below[j];
-            if ((mine >> j & 1u) && row < a.capacity) {   // the capacity covers the worst case (checked on the host): always true
+            const int64_t row = base + points.rank(j);
+            if (points.keeps(j) && row < a.capacity) {    // the capacity covers the worst case (checked on the host): always true
                 uint4 r0, r1;
                 record(a, f, D, L, c, px[j], py[j], r0, r1);
                 a.cloud[2 * row] = r0;

@@ -151,11 +151,6 @@ __global__ __launch_bounds__(256) void color_batch_kernel(const ColorBatch b, co
     }
 }
 
-inline int flat_grid(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" int gwd_color_adjust(const uint8_t *rgb, uint8_t *out, uint64_t *scratch, int64_t npix, int32_t mode, float factor, void *stream) {
@@ -164,15 +159,15 @@ extern "C" int gwd_color_adjust(const uint8_t *rgb, uint8_t *out, uint64_t *scra
     if (mode == 3) {                                          // hue: `factor` carries the uint8 shift itself (0..255), see gwdepth.h
         if (factor < 0.0f || factor > 255.0f) return -1;
         const int shift = (int)factor;
-        hue_kernel<<<flat_grid(npix), 256, 0, s>>>(rgb, out, npix, shift);
+        hue_kernel<<<flat_grid(npix, 4096), 256, 0, s>>>(rgb, out, npix, shift);
     } else {
         if (mode == 1) {
             if (!scratch) return -1;
             hipError_t e = hipMemsetAsync(scratch, 0, sizeof(uint64_t), s);
             if (e != hipSuccess) return (int)e;
-            luma_sum_kernel<<<flat_grid(npix), 256, 0, s>>>(rgb, (unsigned long long *)scratch, npix);
+            luma_sum_kernel<<<flat_grid(npix, 4096), 256, 0, s>>>(rgb, (unsigned long long *)scratch, npix);
         }
-        blend_kernel<<<flat_grid(npix), 256, 0, s>>>(rgb, out, (const unsigned long long *)scratch, npix, mode, factor);
+        blend_kernel<<<flat_grid(npix, 4096), 256, 0, s>>>(rgb, out, (const unsigned long long *)scratch, npix, mode, factor);
     }
     GWD_CHECK_LAUNCH();
     return 0;

@@ -137,10 +137,58 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+// lane src's double, as two 32-bit shuffles
+__device__ __forceinline__ double shfl_d(double v, int src) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const int lo = __shfl((int)(u & 0xffffffffu), src, 64), hi = __shfl((int)(u >> 32), src, 64);
+    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+// one 32x32 MFMA step: bf16 (K = 16, eight elements per lane) or fp32 (K = 2, one per lane)
+__device__ __forceinline__ f32x16 mma(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mma(float a, float b, const f32x16 &c) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+// row of accumulator register i in lane half h (C/D layout of the 32x32 MFMA)
+__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+// The sort key of a score (line_post_kernel's order, line_nms_kernel's): ascending order of the keys = ascending order of the floats,
+// a NaN above everything (torch.sort's rule)
+__device__ __forceinline__ uint32_t score_key(float s) {
+    if (s != s) return 0xffffffffu;
+    const uint32_t u = __builtin_bit_cast(uint32_t, s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// A side of frame b, read from the sizes on the device and clamped to what the host knows of it (the plane, an image's extent): nothing
+// is read outside an operand whatever `sizes` holds.
+__device__ __forceinline__ int frame_side(int size, int limit) { return min(max(size, 0), limit); }
+struct FrameExtent {
+    int fh, fw;
+};
+__device__ __forceinline__ FrameExtent frame_extent(const int32_t *sizes, int b, int Fh, int Fw) {
+    FrameExtent f;
+    f.fh = frame_side(sizes[2 * b], Fh);
+    f.fw = frame_side(sizes[2 * b + 1], Fw);
+    return f;
+}
+
+// workgroups of 256 lanes for a grid-stride kernel over `total` elements, at most `cap`
+inline int flat_grid(int64_t total, int cap) {
+    int64_t b = (total + 255) / 256;
+    return (int)(b > cap ? cap : (b < 1 ? 1 : b));
 }
 
 // Workgroup ids go round-robin over the 8 XCDs (id % 8), each with its own L2.  When `per` consecutive workgroups share one

@@ -48,16 +48,6 @@ Layout layout(int64_t B, int64_t Fh, int64_t Fw) {
     return l;
 }
 
-struct Frame {
-    int fh, fw;
-};
-__device__ __forceinline__ Frame frame_of(const int32_t *sizes, int b, int Fh, int Fw) {
-    Frame f;
-    f.fh = min(max(sizes[2 * b], 0), Fh);
-    f.fw = min(max(sizes[2 * b + 1], 0), Fw);
-    return f;
-}
-
 // ------------------------------------------------------------------------------------------------ ring map and scale sums
 struct RingArgs {
     const uint8_t *labels, *region_map;
@@ -75,7 +65,7 @@ __global__ __launch_bounds__(kThreads) void fusion_row_kernel(const RingArgs a) 
     __shared__ uint8_t tile[kThreads + 2 * kMaxRing];
     const int b = blockIdx.z, y = blockIdx.y, x0 = blockIdx.x * kThreads, t = threadIdx.x;
     if (blockIdx.x == 0 && y == 0 && t < 4) a.sums[b * 4 + t] = 0ull;
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);
     if (y >= f.fh || x0 >= f.fw) return;                  // uniform: the whole workgroup leaves
     const int K = min(max(a.region_count[b], 0), a.max_regions);
     const uint8_t *__restrict__ L = a.labels + b * a.plane + (int64_t)y * a.Fw;
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void fusion_col_kernel(const RingArgs a) 
     __shared__ unsigned long long wsum[3];
     const int b = blockIdx.z, y0 = blockIdx.y * kRows, t = threadIdx.x, lane = t & 63;
     const int x = blockIdx.x * kThreads + t;
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);
     if (t < 3) wsum[t] = 0ull;
     __syncthreads();
     const int64_t base = b * a.plane;
@@ -190,7 +180,7 @@ __global__ __launch_bounds__(kThreads) void fusion_moments_kernel(const FitArgs 
     __shared__ int ox[kMaxR], oy[kMaxR], act[kMaxR];
     __shared__ double c1[kMaxR][3], c2[kMaxR][3], thr[kMaxR];
     const int b = blockIdx.y, blk = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);
     const int K = min(max(a.region_count[b], 0), a.max_regions);
     for (int k = threadIdx.x; k < 4 * kMaxR * kFitNI; k += kThreads) (&pi[0][0][0])[k] = 0;
     for (int k = threadIdx.x; k < 4 * kMaxR * kFitND; k += kThreads) (&pd[0][0][0])[k] = 0.0;
@@ -355,7 +345,7 @@ __global__ __launch_bounds__(kThreads) void fusion_depth_kernel(const FuseArgs a
     __shared__ double coef[kMaxR][3];
     __shared__ int fit[kMaxR];
     const int b = blockIdx.z, y = blockIdx.y, x = (blockIdx.x * kThreads + threadIdx.x) * V;
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);
     if ((int)threadIdx.x < kMaxR) {
         const int r = threadIdx.x;
         const int K = min(max(a.region_count[b], 0), a.max_regions);

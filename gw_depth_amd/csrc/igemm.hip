@@ -113,13 +113,6 @@ __device__ __forceinline__ uint4 row_vec(const T *base, int n, int N, int k0, in
     return *(uint4 *)tmp;
 }
 
-__device__ __forceinline__ f32x16 mma(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mma(float a, float b, const f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 // ----------------------------------------------------------------------------------------------
 // forward / data gradient
 // ----------------------------------------------------------------------------------------------

@@ -34,19 +34,6 @@ struct LineNmsArgs {
     int32_t Q, ld, twin;
 };
 
-__device__ __forceinline__ double shfl_d(double v, int src) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const int lo = __shfl((int)(u & 0xffffffffu), src, 64), hi = __shfl((int)(u >> 32), src, 64);
-    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-// line_post_kernel's key: ascending keys = ascending floats, a NaN above everything
-__device__ __forceinline__ uint32_t score_key(float s) {
-    if (s != s) return 0xffffffffu;
-    const uint32_t u = __builtin_bit_cast(uint32_t, s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // A "slot" names a query of the image or of its twin: slot = query index, + Q for the twin's - the value nms_ids reports.
 // LDS (static, 42 KB): px and sc by slot; cand = the slots that enter, by place; perm = the same in candidate order; keptslot and
 // iv = slot and (start, end) of the r-th kept line.  iv's storage holds the score keys of the merge before the NMS starts.

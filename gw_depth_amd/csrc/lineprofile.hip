@@ -39,12 +39,6 @@ struct ProfileArgs {
     int32_t B, C, Fh, Fw, f64, max_samples, lo_mm, hi_mm, hi, lo;
 };
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // 1 = glass on side a only, 2 = on side b only, 3 = on both, 4 = on neither, 0 = anything else; all in integers
 __device__ __forceinline__ int kind_of(int a_in, int a_glass, int b_in, int b_glass, int hi, int lo) {
     const bool ag = a_in > 0 && 1000 * a_glass >= hi * a_in, an = a_in > 0 && 1000 * a_glass <= lo * a_in;
@@ -75,8 +69,8 @@ __global__ __launch_bounds__(kThreads) void line_profile_kernel(const ProfileArg
             ln = lp_line(ends[0], ends[1], ends[2], ends[3], a.offset, a.max_samples);
             if (ln.n) status = 0;
         }
-        fh = min(max(a.sizes[2 * b], 0), a.Fh);
-        fw = min(max(a.sizes[2 * b + 1], 0), a.Fw);
+        fh = frame_side(a.sizes[2 * b], a.Fh);
+        fw = frame_side(a.sizes[2 * b + 1], a.Fw);
     }
     const int S = status == 0 ? ln.n + 1 : 0;
     const uint8_t *__restrict__ L = a.labels + b * a.plane;

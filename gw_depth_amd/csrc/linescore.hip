@@ -31,12 +31,6 @@ struct LineScoreArgs {
     double nms[LS_MAXT], sap[LS_MAXS];
 };
 
-__device__ __forceinline__ double shfl_d(double v, int src) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const int lo = __shfl((int)(u & 0xffffffffu), src, 64), hi = __shfl((int)(u >> 32), src, 64);
-    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
 // Dynamic LDS: rec[T][Q][2] f64, then px[Q][4] fp32.  rec holds (start, end) of the NMS until the kept lines are written, then
 // (match distance, choice | second-trim bit) of the same line - each record is rewritten only by the thread that owns the line.
 __global__ __launch_bounds__(256) void line_score_kernel(const LineScoreArgs a) {

@@ -113,11 +113,6 @@ __global__ void seg_ce_bwd_kernel(const T *__restrict__ logits, const int64_t *_
     }
 }
 
-inline int flat_grid(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" int gwd_silog_sums(const void *pred, const float *gt, double *sums, int32_t B, int32_t h, int32_t w, int32_t H,
@@ -170,9 +165,9 @@ extern "C" int gwd_seg_ce_sum(const void *logits, const int64_t *target, double 
     if (!logits || !target || !sum || P <= 0) return -1;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == GWD_BF16)
-        seg_ce_sum_kernel<__bf16><<<flat_grid(P), 256, 0, s>>>((const __bf16 *)logits, target, sum, P);
+        seg_ce_sum_kernel<__bf16><<<flat_grid(P, 2048), 256, 0, s>>>((const __bf16 *)logits, target, sum, P);
     else if (dtype == GWD_F32)
-        seg_ce_sum_kernel<float><<<flat_grid(P), 256, 0, s>>>((const float *)logits, target, sum, P);
+        seg_ce_sum_kernel<float><<<flat_grid(P, 2048), 256, 0, s>>>((const float *)logits, target, sum, P);
     else
         return -2;
     GWD_CHECK_LAUNCH();
@@ -184,9 +179,9 @@ extern "C" int gwd_seg_ce_backward(const void *logits, const int64_t *target, co
     if (!logits || !target || !gloss || !glogits || P <= 0) return -1;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == GWD_BF16)
-        seg_ce_bwd_kernel<__bf16><<<flat_grid(P), 256, 0, s>>>((const __bf16 *)logits, target, gloss, scale, (__bf16 *)glogits, P);
+        seg_ce_bwd_kernel<__bf16><<<flat_grid(P, 2048), 256, 0, s>>>((const __bf16 *)logits, target, gloss, scale, (__bf16 *)glogits, P);
     else if (dtype == GWD_F32)
-        seg_ce_bwd_kernel<float><<<flat_grid(P), 256, 0, s>>>((const float *)logits, target, gloss, scale, (float *)glogits, P);
+        seg_ce_bwd_kernel<float><<<flat_grid(P, 2048), 256, 0, s>>>((const float *)logits, target, gloss, scale, (float *)glogits, P);
     else
         return -2;
     GWD_CHECK_LAUNCH();

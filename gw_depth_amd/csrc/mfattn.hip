@@ -52,19 +52,12 @@ template <int HD> struct Geo {
     static constexpr int IMG = 64 * RS;                 // elements per image
 };
 
-__device__ __forceinline__ f32x16 mma(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ f32x16 zero16() {
     f32x16 z;
 #pragma unroll
     for (int i = 0; i < 16; ++i) z[i] = 0.f;
     return z;
 }
-
-// row of accumulator register i in lane half h (C/D layout of the 32x32 MFMA)
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 // ---- global -> registers -> LDS image: lane = token, HD channels, zero-filled to COLS.  Split in two so that the next
 // window's rows are in flight while the current window is being computed.

@@ -300,13 +300,6 @@ __global__ __launch_bounds__(256) void dense_post_resized_kernel(const TD *__res
     }
 }
 
-// ascending order of the keys = ascending order of the floats, a NaN above everything (torch.sort's rule)
-__device__ __forceinline__ uint32_t score_key(float s) {
-    if (s != s) return 0xffffffffu;
-    const uint32_t u = __builtin_bit_cast(uint32_t, s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // One workgroup per image.  The order comes from ranks: query i goes to the place given by the number of queries that beat it
 // (higher key, or equal key and lower index) - a total order, so the ranks are a permutation of 0..Q-1 whatever the scores hold.
 // Every thread reads the same key of the table at a time: LDS broadcasts, Q * ceil(Q / 256) reads per thread.

@@ -83,16 +83,6 @@ __device__ __forceinline__ void unite(int *P, int a, int b) {
     }
 }
 
-struct Frame {
-    int fh, fw;
-};
-__device__ __forceinline__ Frame frame_of(const int32_t *sizes, int b, int Fh, int Fw) {
-    Frame f;
-    f.fh = min(max(sizes[2 * b], 0), Fh);
-    f.fw = min(max(sizes[2 * b + 1], 0), Fw);
-    return f;
-}
-
 struct CcArgs {
     const uint8_t *labels;
     const uint16_t *depth_mm;
@@ -110,7 +100,7 @@ struct CcArgs {
 #define PIXEL_THREAD()                                                 \
     const int b = blockIdx.z, y = blockIdx.y;                           \
     const int x = blockIdx.x * kThreads + threadIdx.x;                  \
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);                   \
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);                   \
     if (y >= f.fh) return;                                              \
     const bool in = x < f.fw;                                           \
     const uint8_t *__restrict__ L = a.labels + b * a.plane;             \
@@ -154,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void cc_merge_kernel(const CcArgs a) {
 #define CHUNK_THREAD()                                                 \
     const int b = blockIdx.z, y0 = blockIdx.y * kRows, lane = threadIdx.x & 63; \
     const int x = blockIdx.x * kThreads + threadIdx.x;                  \
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);                   \
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);                   \
     const int y1 = min(y0 + kRows, f.fh);                               \
     const uint8_t *__restrict__ L = a.labels + b * a.plane;             \
     int *__restrict__ P = a.parent + b * a.plane;                       \
@@ -270,7 +260,7 @@ __global__ __launch_bounds__(kThreads) void cc_records_kernel(const CcArgs a) {
     __shared__ unsigned long long sadd[kMaxR][5];        // area, sum_x, sum_y, n_depth, sum_mm
     __shared__ int smin[kMaxR][3], smax[kMaxR][3];        // x, y, mm
     const int b = blockIdx.z, x = blockIdx.x * kThreads + threadIdx.x, y0 = blockIdx.y * kRows, lane = threadIdx.x & 63;
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);
     const int *__restrict__ P = a.parent + b * a.plane;
     const int *__restrict__ A = a.area + b * a.plane;
     const uint16_t *__restrict__ D = a.depth_mm + b * a.plane;
@@ -388,7 +378,7 @@ __global__ __launch_bounds__(kThreads) void plane_moments_kernel(const PlaneArgs
     __shared__ int ox[kMaxR], oy[kMaxR];
     __shared__ double ca[kMaxR], cb[kMaxR], cg[kMaxR];
     const int b = blockIdx.y, blk = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);
     const int K = min(max(a.region_count[b], 0), a.max_regions);
     for (int k = threadIdx.x; k < 4 * kMaxR * kNI; k += kThreads) (&pi[0][0][0])[k] = 0;
     for (int k = threadIdx.x; k < 4 * kMaxR * kND; k += kThreads) (&pd[0][0][0])[k] = 0.0;
@@ -484,7 +474,7 @@ __global__ __launch_bounds__(kThreads) void depth_planar_kernel(const PlanarArgs
     __shared__ double ca[kMaxR], cb[kMaxR], cg[kMaxR];
     __shared__ int fit[kMaxR];
     const int b = blockIdx.z, y = blockIdx.y, x = blockIdx.x * kThreads + threadIdx.x;
-    const Frame f = frame_of(a.sizes, b, a.Fh, a.Fw);
+    const FrameExtent f = frame_extent(a.sizes, b, a.Fh, a.Fw);
     if ((int)threadIdx.x < kMaxR) {
         const int r = threadIdx.x;
         const int K = min(max(a.region_count[b], 0), a.max_regions);

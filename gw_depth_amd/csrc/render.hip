@@ -50,8 +50,8 @@ __global__ __launch_bounds__(kThreads) void render_frames_kernel(const gwd_rende
     const int b = blockIdx.y;
     const int tiles_x = (d.Fw + kTileW - 1) / kTileW;
     const int x0 = ((int)blockIdx.x % tiles_x) * kTileW, y0 = ((int)blockIdx.x / tiles_x) * kTileH;
-    const int fh = min(max(d.sizes[2 * b], 0), min(d.Fh, d.ext_h[b]));
-    const int fw = min(max(d.sizes[2 * b + 1], 0), min(d.Fw, d.ext_w[b]));
+    const int fh = frame_side(d.sizes[2 * b], min(d.Fh, d.ext_h[b]));
+    const int fw = frame_side(d.sizes[2 * b + 1], min(d.Fw, d.ext_w[b]));
     const int px = x0 + lane;
     const bool tile_live = x0 < fw && y0 < fh;            // uniform
 

@@ -515,10 +515,7 @@ __global__ void stride_place_kernel(const T *__restrict__ src, const T *__restri
     }
 }
 
-inline int flat_grid(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
+constexpr int kGridCap = 8192;      // workgroups of a grid-stride launch (flat_grid)
 
 // the vector kernels dereference uint4 / uint2 at base + k * pitch: a pitched operand (a channel slice of a wider map) must start on a vector
 inline bool misaligned(const void *p, int bytes) { return ((uintptr_t)p % (uintptr_t)bytes) != 0; }
@@ -526,8 +523,8 @@ inline bool misaligned(const void *p, int bytes) { return ((uintptr_t)p % (uintp
 }  // namespace
 
 #define RS_DISPATCH(KERNEL, total, ...)                                                                     \
-    if (dtype == GWD_BF16) KERNEL<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__);  \
-    else if (dtype == GWD_F32) KERNEL<float><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); \
+    if (dtype == GWD_BF16) KERNEL<__bf16><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__);  \
+    else if (dtype == GWD_F32) KERNEL<float><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>(__VA_ARGS__); \
     else return -2;                                                                                         \
     GWD_CHECK_LAUNCH();                                                                                     \
     return 0;
@@ -541,19 +538,19 @@ extern "C" int gwd_resample_forward(const void *x, void *y, int32_t B, int32_t H
     if (C % 4 == 0 && misaligned(y, dtype == GWD_BF16 && C % 8 ? 8 : 16)) return -4;                    // a slice that starts inside a vector
     const int64_t total = (int64_t)B * Ho * Wo * C;
     if (dtype == GWD_BF16 && C % 4 == 0) {
-        if (C % 8 == 0) resample_fwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, Hs, Ws, Ho, Wo, C, mode, ldy);
-        else resample_fwd_vec_kernel<__bf16, 8><<<flat_grid(total / 4), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, Hs, Ws, Ho, Wo, C, mode, ldy);
+        if (C % 8 == 0) resample_fwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, Hs, Ws, Ho, Wo, C, mode, ldy);
+        else resample_fwd_vec_kernel<__bf16, 8><<<flat_grid(total / 4, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, Hs, Ws, Ho, Wo, C, mode, ldy);
         GWD_CHECK_LAUNCH();
         return 0;
     }
     if (dtype == GWD_F32 && C % 4 == 0) {
-        resample_fwd_vec_kernel<float, 16><<<flat_grid(total / 4), 256, 0, (hipStream_t)stream>>>((const float *)x, (float *)y, B, Hs, Ws, Ho, Wo, C, mode, ldy);
+        resample_fwd_vec_kernel<float, 16><<<flat_grid(total / 4, kGridCap), 256, 0, (hipStream_t)stream>>>((const float *)x, (float *)y, B, Hs, Ws, Ho, Wo, C, mode, ldy);
         GWD_CHECK_LAUNCH();
         return 0;
     }
     if (ldy != C) return -4;
-    if (dtype == GWD_BF16) resample_fwd_kernel<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, Hs, Ws, Ho, Wo, C, mode);
-    else if (dtype == GWD_F32) resample_fwd_kernel<float><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const float *)x, (float *)y, B, Hs, Ws, Ho, Wo, C, mode);
+    if (dtype == GWD_BF16) resample_fwd_kernel<__bf16><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, Hs, Ws, Ho, Wo, C, mode);
+    else if (dtype == GWD_F32) resample_fwd_kernel<float><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const float *)x, (float *)y, B, Hs, Ws, Ho, Wo, C, mode);
     else return -2;
     GWD_CHECK_LAUNCH();
     return 0;
@@ -567,18 +564,18 @@ extern "C" int gwd_resample_backward(const void *gy, void *gx, int32_t B, int32_
     const int64_t total = (int64_t)B * Hs * Ws * C;
     if (mode == MODE_NEAREST && dtype == GWD_BF16 && C % 4 == 0) {
         hipStream_t s = (hipStream_t)stream;
-        if (C % 8 == 0) resample_nearest_bwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8), 256, 0, s>>>((const __bf16 *)gy, (__bf16 *)gx, B, Hs, Ws, Ho, Wo, C, (const __bf16 *)gate, gate_act);
-        else resample_nearest_bwd_vec_kernel<__bf16, 8><<<flat_grid(total / 4), 256, 0, s>>>((const __bf16 *)gy, (__bf16 *)gx, B, Hs, Ws, Ho, Wo, C, (const __bf16 *)gate, gate_act);
+        if (C % 8 == 0) resample_nearest_bwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8, kGridCap), 256, 0, s>>>((const __bf16 *)gy, (__bf16 *)gx, B, Hs, Ws, Ho, Wo, C, (const __bf16 *)gate, gate_act);
+        else resample_nearest_bwd_vec_kernel<__bf16, 8><<<flat_grid(total / 4, kGridCap), 256, 0, s>>>((const __bf16 *)gy, (__bf16 *)gx, B, Hs, Ws, Ho, Wo, C, (const __bf16 *)gate, gate_act);
         GWD_CHECK_LAUNCH();
         return 0;
     }
     if (mode == MODE_NEAREST && dtype == GWD_F32 && C % 4 == 0) {
-        resample_nearest_bwd_vec_kernel<float, 16><<<flat_grid(total / 4), 256, 0, (hipStream_t)stream>>>((const float *)gy, (float *)gx, B, Hs, Ws, Ho, Wo, C, (const float *)gate, gate_act);
+        resample_nearest_bwd_vec_kernel<float, 16><<<flat_grid(total / 4, kGridCap), 256, 0, (hipStream_t)stream>>>((const float *)gy, (float *)gx, B, Hs, Ws, Ho, Wo, C, (const float *)gate, gate_act);
         GWD_CHECK_LAUNCH();
         return 0;
     }
-    if (dtype == GWD_BF16) resample_bwd_kernel<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gy, (__bf16 *)gx, B, Hs, Ws, Ho, Wo, C, mode);
-    else if (dtype == GWD_F32) resample_bwd_kernel<float><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const float *)gy, (float *)gx, B, Hs, Ws, Ho, Wo, C, mode);
+    if (dtype == GWD_BF16) resample_bwd_kernel<__bf16><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gy, (__bf16 *)gx, B, Hs, Ws, Ho, Wo, C, mode);
+    else if (dtype == GWD_F32) resample_bwd_kernel<float><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const float *)gy, (float *)gx, B, Hs, Ws, Ho, Wo, C, mode);
     else return -2;
     GWD_CHECK_LAUNCH();
     return 0;
@@ -589,13 +586,13 @@ extern "C" int gwd_avgpool_forward(const void *x, void *y, int32_t B, int32_t H,
     if (!x || !y || B <= 0 || H < k || W < k || C <= 0 || k <= 0) return -1;
     const int64_t total = (int64_t)B * (H / k) * (W / k) * C;
     if (dtype == GWD_BF16 && C % 4 == 0) {
-        if (C % 8 == 0) avgpool_fwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, H, W, C, k);
-        else avgpool_fwd_vec_kernel<__bf16, 8><<<flat_grid(total / 4), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, H, W, C, k);
+        if (C % 8 == 0) avgpool_fwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, H, W, C, k);
+        else avgpool_fwd_vec_kernel<__bf16, 8><<<flat_grid(total / 4, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, H, W, C, k);
         GWD_CHECK_LAUNCH();
         return 0;
     }
-    if (dtype == GWD_BF16) avgpool_fwd_kernel<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, H, W, C, k);
-    else if (dtype == GWD_F32) avgpool_fwd_kernel<float><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const float *)x, (float *)y, B, H, W, C, k);
+    if (dtype == GWD_BF16) avgpool_fwd_kernel<__bf16><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)x, (__bf16 *)y, B, H, W, C, k);
+    else if (dtype == GWD_F32) avgpool_fwd_kernel<float><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const float *)x, (float *)y, B, H, W, C, k);
     else return -2;
     GWD_CHECK_LAUNCH();
     return 0;
@@ -606,13 +603,13 @@ extern "C" int gwd_avgpool_backward(const void *gy, void *gx, int32_t B, int32_t
     if (!gy || !gx || B <= 0 || H < k || W < k || C <= 0 || k <= 0) return -1;
     const int64_t total = (int64_t)B * H * W * C;
     if (dtype == GWD_BF16 && C % 4 == 0) {
-        if (C % 8 == 0) avgpool_bwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gy, (__bf16 *)gx, B, H, W, C, k);
-        else avgpool_bwd_vec_kernel<__bf16, 8><<<flat_grid(total / 4), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gy, (__bf16 *)gx, B, H, W, C, k);
+        if (C % 8 == 0) avgpool_bwd_vec_kernel<__bf16, 16><<<flat_grid(total / 8, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gy, (__bf16 *)gx, B, H, W, C, k);
+        else avgpool_bwd_vec_kernel<__bf16, 8><<<flat_grid(total / 4, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gy, (__bf16 *)gx, B, H, W, C, k);
         GWD_CHECK_LAUNCH();
         return 0;
     }
-    if (dtype == GWD_BF16) avgpool_bwd_kernel<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gy, (__bf16 *)gx, B, H, W, C, k);
-    else if (dtype == GWD_F32) avgpool_bwd_kernel<float><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const float *)gy, (float *)gx, B, H, W, C, k);
+    if (dtype == GWD_BF16) avgpool_bwd_kernel<__bf16><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gy, (__bf16 *)gx, B, H, W, C, k);
+    else if (dtype == GWD_F32) avgpool_bwd_kernel<float><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const float *)gy, (float *)gx, B, H, W, C, k);
     else return -2;
     GWD_CHECK_LAUNCH();
     return 0;
@@ -630,12 +627,12 @@ extern "C" int gwd_resample_backward_sep(const void *gy, float *tmp, void *gx, i
     const int vec = (dtype == GWD_BF16 && C % 8 == 0) ? 8 : 4;
     const int64_t t1 = (int64_t)B * Ho * Ws * (C / vec), t2 = (int64_t)B * Hs * Ws * (C / 4);
     if (dtype == GWD_BF16) {
-        if (vec == 8) resample_bwd_x_kernel<__bf16, 16><<<flat_grid(t1), 256, 0, st>>>((const __bf16 *)gy, tmp, B, Ws, Ho, Wo, C, mode, ldg);
-        else resample_bwd_x_kernel<__bf16, 8><<<flat_grid(t1), 256, 0, st>>>((const __bf16 *)gy, tmp, B, Ws, Ho, Wo, C, mode, ldg);
-        resample_bwd_y_kernel<__bf16><<<flat_grid(t2), 256, 0, st>>>(tmp, (__bf16 *)gx, B, Hs, Ws, Ho, C, mode);
+        if (vec == 8) resample_bwd_x_kernel<__bf16, 16><<<flat_grid(t1, kGridCap), 256, 0, st>>>((const __bf16 *)gy, tmp, B, Ws, Ho, Wo, C, mode, ldg);
+        else resample_bwd_x_kernel<__bf16, 8><<<flat_grid(t1, kGridCap), 256, 0, st>>>((const __bf16 *)gy, tmp, B, Ws, Ho, Wo, C, mode, ldg);
+        resample_bwd_y_kernel<__bf16><<<flat_grid(t2, kGridCap), 256, 0, st>>>(tmp, (__bf16 *)gx, B, Hs, Ws, Ho, C, mode);
     } else {
-        resample_bwd_x_kernel<float, 16><<<flat_grid(t1), 256, 0, st>>>((const float *)gy, tmp, B, Ws, Ho, Wo, C, mode, ldg);
-        resample_bwd_y_kernel<float><<<flat_grid(t2), 256, 0, st>>>(tmp, (float *)gx, B, Hs, Ws, Ho, C, mode);
+        resample_bwd_x_kernel<float, 16><<<flat_grid(t1, kGridCap), 256, 0, st>>>((const float *)gy, tmp, B, Ws, Ho, Wo, C, mode, ldg);
+        resample_bwd_y_kernel<float><<<flat_grid(t2, kGridCap), 256, 0, st>>>(tmp, (float *)gx, B, Hs, Ws, Ho, C, mode);
     }
     GWD_CHECK_LAUNCH();
     return 0;
@@ -667,9 +664,9 @@ extern "C" int gwd_psp_pool_backward(const void *gpass, const void *g16, const v
     if (C % vec || ldg % vec || ldg < C || misaligned(gpass, 16)) return -4;
     const int64_t total = (int64_t)B * H * W * (C / vec);
     if (dtype == GWD_BF16)
-        psp_pool_bwd_kernel<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gpass, (const __bf16 *)g16, (const __bf16 *)g8, (const __bf16 *)g4, (const __bf16 *)g2, (__bf16 *)gx, B, H, W, C, ldg);
+        psp_pool_bwd_kernel<__bf16><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)gpass, (const __bf16 *)g16, (const __bf16 *)g8, (const __bf16 *)g4, (const __bf16 *)g2, (__bf16 *)gx, B, H, W, C, ldg);
     else
-        psp_pool_bwd_kernel<float><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const float *)gpass, (const float *)g16, (const float *)g8, (const float *)g4, (const float *)g2, (float *)gx, B, H, W, C, ldg);
+        psp_pool_bwd_kernel<float><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const float *)gpass, (const float *)g16, (const float *)g8, (const float *)g4, (const float *)g2, (float *)gx, B, H, W, C, ldg);
     GWD_CHECK_LAUNCH();
     return 0;
 }
@@ -682,9 +679,9 @@ extern "C" int gwd_stride_place(const void *src, const void *residual, void *dst
     if (C % vec) return -4;
     const int64_t total = (int64_t)B * H * W * (C / vec);
     if (dtype == GWD_BF16)
-        stride_place_kernel<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const __bf16 *)src, (const __bf16 *)residual, (__bf16 *)dst, B, H, W, Ho, Wo, C, stride);
+        stride_place_kernel<__bf16><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const __bf16 *)src, (const __bf16 *)residual, (__bf16 *)dst, B, H, W, Ho, Wo, C, stride);
     else
-        stride_place_kernel<float><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>((const float *)src, (const float *)residual, (float *)dst, B, H, W, Ho, Wo, C, stride);
+        stride_place_kernel<float><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>((const float *)src, (const float *)residual, (float *)dst, B, H, W, Ho, Wo, C, stride);
     GWD_CHECK_LAUNCH();
     return 0;
 }
@@ -729,9 +726,9 @@ extern "C" int gwd_upsample_taps_collapse(const float *w, void *wk, int32_t Cout
     if (!w || !wk || Cout <= 0 || Cin <= 0 || (int64_t)Cout * Cin * 16 > INT32_MAX) return -1;
     const int64_t total = (int64_t)Cin * 16 * Cout;
     if (dtype == GWD_BF16)
-        ups_taps_collapse_kernel<__bf16><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>(w, (__bf16 *)wk, Cout, Cin);
+        ups_taps_collapse_kernel<__bf16><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>(w, (__bf16 *)wk, Cout, Cin);
     else if (dtype == GWD_F32)
-        ups_taps_collapse_kernel<float><<<flat_grid(total), 256, 0, (hipStream_t)stream>>>(w, (float *)wk, Cout, Cin);
+        ups_taps_collapse_kernel<float><<<flat_grid(total, kGridCap), 256, 0, (hipStream_t)stream>>>(w, (float *)wk, Cout, Cin);
     else
         return -2;
     GWD_CHECK_LAUNCH();
@@ -740,7 +737,7 @@ extern "C" int gwd_upsample_taps_collapse(const float *w, void *wk, int32_t Cout
 
 extern "C" int gwd_upsample_taps_fold(const float *D, float *dw, int32_t Cout, int32_t Cin, void *stream) {
     if (!D || !dw || Cout <= 0 || Cin <= 0 || (int64_t)Cout * Cin * 16 > INT32_MAX) return -1;
-    ups_taps_fold_kernel<<<flat_grid((int64_t)Cout * 9 * Cin), 256, 0, (hipStream_t)stream>>>(D, dw, Cout, Cin);
+    ups_taps_fold_kernel<<<flat_grid((int64_t)Cout * 9 * Cin, kGridCap), 256, 0, (hipStream_t)stream>>>(D, dw, Cout, Cin);
     GWD_CHECK_LAUNCH();
     return 0;
 }

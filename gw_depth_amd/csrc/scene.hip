@@ -27,7 +27,7 @@
 // voxel's rank is a function of (serial, row) alone, not of the slot its key landed in: results are bit-identical from run to run.  No
 // thread waits for another: a probe visits at most `slots` slots, accumulators start as zeros so a joined slot needs no
 // initialisation, and there is no "being initialised" state.
-#include "common.h"
+#include "compact.h"
 
 // tests/scene_ref.py rounds after every operation; hipcc would contract a * b + c
 #pragma clang fp contract(off)
@@ -37,7 +37,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kRounds = GWD_SCENE_TILE / kThreads;
-constexpr int kScanThreads = 1024;
 constexpr int kResetBlocks = 2048;
 constexpr unsigned long long kEmpty = ~0ull;
 constexpr int kBias = 1 << 20;                            // a voxel index is -2^20 .. 2^20 - 1
@@ -187,31 +186,6 @@ __global__ __launch_bounds__(kThreads) void scene_count_kernel(const SceneArgs a
     }
 }
 
-// one workgroup: `counts` [tiles] -> exclusive offsets in place, [tiles] the total; thread t owns `chunk` consecutive tiles
-__device__ __forceinline__ void scan_tiles(int32_t *counts, int tiles, int *sums) {
-    const int t = threadIdx.x;
-    const int chunk = (tiles + kScanThreads - 1) / kScanThreads;
-    const int lo = min(t * chunk, tiles), hi = min(lo + chunk, tiles);
-    int mine = 0;
-    for (int k = lo; k < hi; ++k) mine += counts[k];
-    sums[t] = mine;
-    __syncthreads();
-    for (int o = 1; o < kScanThreads; o <<= 1) {          // inclusive, Hillis-Steele
-        const int v = t >= o ? sums[t - o] : 0;
-        __syncthreads();
-        sums[t] += v;
-        __syncthreads();
-    }
-    int run = sums[t] - mine;
-    for (int k = lo; k < hi; ++k) {
-        const int c = counts[k];
-        counts[k] = run;
-        run += c;
-    }
-    if (t == kScanThreads - 1) counts[tiles] = sums[t];
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(kScanThreads) void scene_scan_kernel(const SceneArgs a) {
     __shared__ int sums[kScanThreads];
     const int t = threadIdx.x;
@@ -247,36 +221,22 @@ __global__ __launch_bounds__(kThreads) void scene_rank_kernel(const SceneArgs a)
     if (!a.call[2]) return;                               // uniform: overflow, the contents are undefined from here on
     const int64_t total = total_rows(a);
     const long long serial = a.call[0];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int32_t slot[kRounds];
-    int below[kRounds];
-    unsigned mine = 0u;
+    TileRank<kRounds, kWaves> births;
 #pragma unroll
     for (int j = 0; j < kRounds; ++j) {
         const int64_t row = (int64_t)blockIdx.x * GWD_SCENE_TILE + j * kThreads + threadIdx.x;
         slot[j] = row < total ? a.slot_of[row] : kNoSlot;
-        const bool born = row < total && is_birth(a, serial, row, slot[j]);
-        const unsigned long long m = __ballot(born);
-        below[j] = __popcll(m & ((1ull << lane) - 1ull));
-        if (born) mine |= 1u << j;
-        if (lane == 0) part[j * kWaves + wave] = __popcll(m);
+        births.vote(j, row < total && is_birth(a, serial, row, slot[j]), part);
     }
     __syncthreads();
-    if (!mine) return;
+    if (!births.any()) return;
     const long long base = a.call[1] + a.births[blockIdx.x];
-    int before = 0;                                       // the births of the rounds and waves ahead of this one
+    births.finish(part);
 #pragma unroll
     for (int j = 0; j < kRounds; ++j) {
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            if (w == wave) below[j] += before;
-            before += part[j * kWaves + w];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-        const long long rank = base + below[j];
-        if ((mine >> j & 1u) && rank < a.max_voxels) {    // the scan has checked count + born <= max_voxels: always true
+        const long long rank = base + births.rank(j);
+        if (births.keeps(j) && rank < a.max_voxels) {     // the scan has checked count + born <= max_voxels: always true
             a.ranks[slot[j]] = (int32_t)rank;             // only this row reads or writes the rank of its slot in this launch
             a.voxels[rank].key = a.keys[slot[j]];
             a.voxels[rank].first_seen = (int32_t)serial;
@@ -383,14 +343,7 @@ __global__ __launch_bounds__(kThreads) void scene_keep_kernel(const SceneArgs a)
     int n = 0;
 #pragma unroll
     for (int j = 0; j < kRounds; ++j) n += __popcll(__ballot(kept(a, (int64_t)blockIdx.x * GWD_SCENE_TILE + j * kThreads + threadIdx.x, count)));
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) t += part[w];
-        a.births[blockIdx.x] = t;
-    }
+    tile_sum<kWaves>(n, part, &a.births[blockIdx.x]);
 }
 
 __global__ __launch_bounds__(kScanThreads) void scene_keep_scan_kernel(const SceneArgs a) {
@@ -431,33 +384,17 @@ __device__ __forceinline__ void merged_record(const SceneArgs &a, const Voxel &v
 __global__ __launch_bounds__(kThreads) void scene_emit_kernel(const SceneArgs a) {
     __shared__ int part[kRounds * kWaves];
     const long long count = live_count(a);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int below[kRounds];
-    unsigned mine = 0u;
+    TileRank<kRounds, kWaves> voxels;
 #pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-        const bool ok = kept(a, (int64_t)blockIdx.x * GWD_SCENE_TILE + j * kThreads + threadIdx.x, count);
-        const unsigned long long m = __ballot(ok);
-        below[j] = __popcll(m & ((1ull << lane) - 1ull));
-        if (ok) mine |= 1u << j;
-        if (lane == 0) part[j * kWaves + wave] = __popcll(m);
-    }
+    for (int j = 0; j < kRounds; ++j) voxels.vote(j, kept(a, (int64_t)blockIdx.x * GWD_SCENE_TILE + j * kThreads + threadIdx.x, count), part);
     __syncthreads();
-    if (mine) {
+    if (voxels.any()) {
         const int64_t base = a.births[blockIdx.x];
-        int before = 0;
+        voxels.finish(part);
 #pragma unroll
         for (int j = 0; j < kRounds; ++j) {
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                if (w == wave) below[j] += before;
-                before += part[j * kWaves + w];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kRounds; ++j) {
-            const int64_t row = base + below[j];
-            if ((mine >> j & 1u) && row < a.max_voxels) {
+            const int64_t row = base + voxels.rank(j);
+            if (voxels.keeps(j) && row < a.max_voxels) {
                 uint4 r0, r1;
                 int4 st;
                 merged_record(a, a.voxels[(int64_t)blockIdx.x * GWD_SCENE_TILE + j * kThreads + threadIdx.x], r0, r1, st);

@@ -20,11 +20,6 @@ constexpr int PR = 39;                 // patch rows: 2 * 16 + 7
 constexpr int PXS = 15, PYS = 8;       // pooled columns / rows per workgroup
 constexpr int NT = 256;
 
-__device__ __forceinline__ f32x16 mma(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
 __global__ __launch_bounds__(NT, 2) void stem_kernel(const __bf16 *__restrict__ x, const __bf16 *__restrict__ w, const float *__restrict__ shift,
                                                   __bf16 *__restrict__ y, int B, int H, int W, int Hc, int Wc, int Hp, int Wp, int tiles_y,
                                                   int tiles_x, int ntiles) {

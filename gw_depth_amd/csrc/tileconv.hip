@@ -22,11 +22,6 @@ constexpr int TW = 32, HW = TW + 2;            // output tile width, halo width;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-__device__ __forceinline__ f32x16 mma(const bf16x8 &a, const bf16x8 &b, const f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
 template <int CIN, int TH, int RPW = 2> struct Halo {
     static constexpr int HH = TH + 2, HPIX = HH * HW;       // halo rows / pixels
     static constexpr int NT = 64 * TH / RPW;                // threads: one wave per RPW output rows

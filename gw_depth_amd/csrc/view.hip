@@ -130,8 +130,8 @@ __global__ __launch_bounds__(kThreads) void view_splat_kernel(const ViewArgs a) 
             c.t[i] = a.poses[12 * v + 4 * i + 3];
         }
     }
-    c.fh = min(max(a.sizes[2 * v], 0), a.ext_h[v]);
-    c.fw = min(max(a.sizes[2 * v + 1], 0), a.ext_w[v]);
+    c.fh = frame_side(a.sizes[2 * v], a.ext_h[v]);
+    c.fw = frame_side(a.sizes[2 * v + 1], a.ext_w[v]);
     unsigned long long *plane = a.zbuf + (int64_t)v * a.Fh * a.Fw;
     const int lane = threadIdx.x & 63;
 #pragma unroll 1

@@ -125,6 +125,28 @@ def test_same_frame_same_rows_in_another_slot_and_plane():
     assert a.tobytes() == b.tobytes()
 
 
+def test_scan_thread_owns_two_tiles():
+    """More tiles than the scan workgroup has threads: 513 + 514 tiles, so a scan thread owns two, the frame boundary (block 513)
+    falls inside one thread's pair, thread 513 owns a single tile and the threads above it none."""
+    T = hip.CLOUD_TILE
+    sizes = [(749, 700), (750, 701)]
+    per_frame = [-(-h * w // T) for h, w in sizes]
+    tiles = sum(per_frame)
+    assert tiles > 1024 and tiles % 2 == 1 and per_frame[0] % 2 == 1          # a changed tile size cannot empty the case
+    rng = np.random.default_rng(513)
+    depth = rng.uniform(0.5, 7.5, (2, 750, 701)).astype(np.float32)
+    depth[rng.random(depth.shape) < 0.3] = 0.0
+    labels = rng.integers(0, 256, depth.shape, dtype=np.uint8)
+    cam = np.array([(600.0, 610.0, 350.0, 374.0), (590.0, 585.0, 352.5, 371.0)], np.float64)
+    kw = dict(stride=1, min_depth=K.MIN_DEPTH, max_depth=K.MAX_DEPTH, normals=True)
+    want = C.point_cloud(depth, labels, np.array(sizes, np.int32), cam, **kw)
+    out = run(depth, labels, np.array(sizes, np.int32), cam, frame_sizes=sizes, **kw)
+    total = int(want["cloud_offsets"][-1])
+    assert 0.6 * 749 * 700 < int(want["cloud_offsets"][1]) < 749 * 700 and total < out["cloud"].shape[0]
+    differ, comps = check(out, want, "1027 tiles")
+    print("1027 tiles: %d points, %d of %d normal components differ at all" % (total, differ, comps))
+
+
 def test_session_end_to_end():
     """Two synthetic frames through InferenceSession(regions, fusion, cloud).predict_frames(sensor_depth, intrinsics, poses): the cloud
     equals ops.point_cloud applied to the returned tensors (bit for bit) and the statement under the bounds above; every other key

@@ -132,6 +132,23 @@ def test_contention(cells):
     assert int(out["cloud_offsets"][1]) == cells and out["voxel_stats"][:cells, 0].sum() == 5003 and state["points"] == 5003
 
 
+def test_scan_thread_owns_two_tiles():
+    """More tiles than a scan workgroup has threads, in the cloud's rows (the integrate scan) and in max_voxels (the extract scan):
+    a scan thread owns two tiles.  5003 voxels are born in the first tiles, every later tile counts zero, and the second call has no
+    births at all."""
+    rows = max_voxels = 1024 * 1024 + 4097
+    tiles = -(-rows // hip.SCENE_TILE)
+    assert tiles > 1024                                   # a changed tile size cannot empty the case
+    cloud = K.as_cloud(K.distinct_voxels(5003), capacity=rows)
+    options = ({}, dict(min_obs=2))
+    ref = S.SceneMap(0.1, max_voxels).integrate(*cloud).integrate(*cloud)
+    outs, state, _, _ = run([cloud, cloud], 0.1, max_voxels, options=options)
+    for out, opt in zip(outs, options):
+        check(out, ref.extract(**opt), "1029 tiles %r" % (opt,))
+    assert int(outs[0]["cloud_offsets"][1]) == int(outs[1]["cloud_offsets"][1]) == 5003
+    assert state == ref.state() == dict(serial=2, count=5003, points=10006, dropped=0, status=0)
+
+
 @pytest.mark.parametrize("name", list(K.EDGES))
 def test_arithmetic_edges_by_hand(name):
     case = K.EDGES[name]

@@ -385,7 +385,10 @@ def test_header_binding_and_makefile_agree():
     assert (F.SENSOR, F.PLANE, F.NETWORK) == (hip.FUSED_SENSOR, hip.FUSED_PLANE, hip.FUSED_NETWORK)
     assert len(F.PLANE_FIELDS) == hip.FUSION_PLANE and F.PLANE_FIELDS == ops.FUSION_PLANE_FIELDS
     make = open(os.path.join(ROOT, "gw_depth_amd", "csrc", "Makefile")).read()
-    assert "fusion.hip" in make and re.search(r"regions\.o fusion\.o: planefit\.h", make)
+    # regions.o and fusion.o follow planefit.h through the dependencies the compiler writes: the flags ask for them, the Makefile
+    # reads them, and both sources include the header
+    assert "fusion.hip" in make and re.search(r"^CXXFLAGS\b.*-MMD", make, re.M) and re.search(r"^-include \$\(OBJS:\.o=\.d\)", make, re.M)
+    assert '#include "planefit.h"' in open(os.path.join(ROOT, "gw_depth_amd", "csrc", "fusion.hip")).read()
     for name in ("gwd_fusion_ring", "gwd_fusion_planes", "gwd_fusion_depth"):
         assert name in hip.ENTRY_POINTS and name in header
     regions = open(os.path.join(ROOT, "gw_depth_amd", "csrc", "regions.hip")).read()     # the fit is written once, in the header
